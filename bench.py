@@ -4,7 +4,13 @@ BASELINE.json config 4 (128-plane 1024x1024 MPI, 1000-pose camera path,
 view-sharded), with the dominant kernel's roofline and the CPU restatement timed on
 the same host, plus one leg per other BASELINE config and the notebook's own shape.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--views V] [--legs c4,sv,...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--views V] [--dump-outputs DIR]
+                    [--full [--legs c4,sv,...]]
+
+A plain run does only what the headline needs: it sets up the config-4 inputs, warms up,
+times the K steps, writes the last step's frames when --dump-outputs is given, and prints
+the result line.  Everything else -- the other legs, the CPU baseline, the frame checks,
+the gather ceiling and census of the roofline, the rocprof quotes -- runs under --full.
 
 Launch.  One process per GPU.  `--gpus N > 1` without a torchrun environment starts
 N ranks itself (a `torch.distributed.run` child, before this process touches the GPU)
@@ -38,7 +44,7 @@ kernel and grid its launch routes to (mpiv_route) and, when the summary's build 
 matches this library, quotes rocprof's average duration and the PMC HBM traffic of
 exactly those dispatches next to its own HIP-event time.
 
-Legs (--legs, default all): c4 (headline), sv (single view), c2 (config 2: 64 views
+Legs (--full; --legs, default all): c4 (headline), sv (single view), c2 (config 2: 64 views
 of a 1024x576x32 MPI), c3 (config 3: PSV of 5 sources into 64 planes through
 plane_sweep_torch), nb (the notebook's 224x224x10 render + training step + PSV),
 u8 (8-bit texels: config-4-shape u8 MPI, one view and V views per launch), netout (the
@@ -82,7 +88,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--views", type=int, default=125, help="views rendered per GPU per step")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample budget (0 = skip)")
-    ap.add_argument("--legs", default=",".join(ALL_LEGS), help="comma list of " + ",".join(ALL_LEGS))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the other legs, the CPU baseline, the frame checks and the roofline's live "
+                         "measurements (default: the timed config-4 steps only)")
+    ap.add_argument("--legs", default=None, help="with --full: comma list of " + ",".join(ALL_LEGS) + " (default all)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frames of the last timed step to DIR/*.npy (float32; see dump_outputs)")
     ap.add_argument("--no-config5", action="store_true", help="skip the config-5 leg")
     ap.add_argument("--no-training", action="store_true", help="skip the training leg")
     ap.add_argument("--no-extras", action="store_true", help="only the timed config-4 launches")
@@ -90,11 +101,13 @@ def parse():
                     help="packed: the production packed-MPI route (default); native: the reference layout "
                          "read in place (mpiv_render)")
     a = ap.parse_args()
-    legs = [x for x in a.legs.split(",") if x]
+    if a.legs is not None and not a.full:
+        ap.error("--legs selects among the legs of a --full run: add --full")
+    legs = [x for x in a.legs.split(",") if x] if a.legs is not None else list(ALL_LEGS)
     bad = [x for x in legs if x not in ALL_LEGS]
     if bad:
         ap.error(f"unknown legs {bad}")
-    if a.no_extras:
+    if a.no_extras or not a.full:
         legs = [x for x in legs if x == "c4"]
     if a.no_config5:
         legs = [x for x in legs if x != "c5"]
@@ -400,6 +413,25 @@ def gen_view(H, W, P, seed, dev):
     v[..., :3].mul_(2.0).sub_(1.0)
     v[:, :, 0, 3] = 1.0
     return v
+
+
+DUMP_VIEWS = 3           # whole frames written by --dump-outputs (views 0, V/2, V-1)
+DUMP_SAMPLE = 1 << 22    # elements of the seeded sample over all V frames
+
+
+def dump_outputs(path: str, out: torch.Tensor):
+    """--dump-outputs: the frames [V,H,W,3] the last timed step left in `out` (what a caller of
+    the render receives), as float32 .npy files in `path`.  A whole 125-view step is 1.5 GB, so
+    it is written as a fixed selection that is the same for every run with the same arguments
+    (under 64 MB at config 4): frames.npy, views 0, V/2 and V-1 whole, and frames_sample.npy,
+    DUMP_SAMPLE elements of the flattened [V,H,W,3] output at seeded (seed 0) random offsets."""
+    os.makedirs(path, exist_ok=True)
+    V = out.shape[0]
+    views = sorted({0, V // 2, V - 1})[:DUMP_VIEWS]
+    np.save(os.path.join(path, "frames.npy"), out[views].cpu().numpy())
+    flat = out.reshape(-1)
+    idx = torch.randint(0, flat.numel(), (min(DUMP_SAMPLE, flat.numel()),), generator=torch.Generator().manual_seed(0))
+    np.save(os.path.join(path, "frames_sample.npy"), flat[idx.to(out.device)].cpu().numpy())
 
 
 def hbm(alg_bytes, ms):
@@ -1219,6 +1251,8 @@ def main():
     kern_ms_local = float(np.mean([a.elapsed_time(b) for a, b in events]))
     kern_all = all_ranks(kern_ms_local, world, dev)
     kern_ms = max(kern_all)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     # --- after the timed region: the last timed launch's first frame against a one-view
     # launch of the same pose (bit-exact), the gather ceiling, the census
@@ -1258,7 +1292,7 @@ def main():
     hbm_alg_bytes = V * (P * H * W * 16 + H * W * 12)  # every view reading its MPI once (§8d)
     gather_bytes = gathers * kWaveBytes if gathers else tap_bytes
     achieved = gather_bytes / (kern_ms * 1e-3) / 1e9
-    pf = prof_fields(kernel_name, grid, hbm_alg_bytes, kern_ms, "c4")
+    pf = prof_fields(kernel_name, grid, hbm_alg_bytes, kern_ms, "c4") if args.full else {}
     traffic = pf.get("traffic")
 
     cpu_frames, cpu_view = None, None

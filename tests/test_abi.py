@@ -147,17 +147,18 @@ def test_output_buffers_validated():
 
 
 @pytest.mark.slow
-def test_host_asan_builds():
+def test_host_asan_builds(tmp_path):
     """Host AddressSanitizer + UBSan flavour (GPU ASan is not available on
     this pool): an ASan-instrumented libmpiv driven through every argument-validation
     path and the host homography chain, and the CPU oracle on small / degenerate inputs
-    (tools/asan/Makefile, built into /tmp)."""
+    (tools/asan/Makefile, built into the test's own temporary directory: a fixed directory
+    may be left over from another user's run and not be writable)."""
     import shutil
     import subprocess
     if shutil.which("/opt/rocm/bin/hipcc") is None or shutil.which("gcc") is None:
         pytest.skip("needs hipcc and gcc")
-    r = subprocess.run(["make", "-s", "-C", os.path.join(REPO, "tools", "asan"), "run"], capture_output=True,
-                       text=True, timeout=600)
+    r = subprocess.run(["make", "-s", "-C", os.path.join(REPO, "tools", "asan"), "run", f"OUT={tmp_path}"],
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "abi_check: 0 failure(s)" in r.stdout and "oracle_check: ok" in r.stdout
 

@@ -21,13 +21,69 @@ def _parse(monkeypatch, *argv):
 
 
 def test_leg_selection(monkeypatch):
-    assert _parse(monkeypatch).legs == list(bench.ALL_LEGS)
-    assert _parse(monkeypatch, "--no-extras").legs == ["c4"]
-    a = _parse(monkeypatch, "--no-config5", "--no-training", "--cpu-seconds", "0")
-    assert a.legs == ["c4", "sv", "c2", "c3", "nb", "u8", "netout"]
-    assert _parse(monkeypatch, "--legs", "c3").legs == ["c3"]
+    # a plain run times the headline only; every other leg belongs to --full
+    assert _parse(monkeypatch).legs == ["c4"]
+    assert _parse(monkeypatch, "--steps", "7", "--warmup", "3", "--dump-outputs", "d").legs == ["c4"]
+    assert _parse(monkeypatch, "--no-config5", "--no-training", "--cpu-seconds", "0").legs == ["c4"]
     with pytest.raises(SystemExit):
-        _parse(monkeypatch, "--legs", "c9")
+        _parse(monkeypatch, "--legs", "c3")
+    assert _parse(monkeypatch, "--full").legs == list(bench.ALL_LEGS)
+    assert _parse(monkeypatch, "--full", "--no-extras").legs == ["c4"]
+    a = _parse(monkeypatch, "--full", "--no-config5", "--no-training", "--cpu-seconds", "0")
+    assert a.legs == ["c4", "sv", "c2", "c3", "nb", "u8", "netout"]
+    assert _parse(monkeypatch, "--full", "--legs", "c3").legs == ["c3"]
+    with pytest.raises(SystemExit):
+        _parse(monkeypatch, "--full", "--legs", "c9")
+
+
+def test_dump_outputs_writes_a_fixed_selection(tmp_path):
+    """--dump-outputs: three whole frames plus a seeded sample of the step's output, float32,
+    the same selection on every call (two builds are compared file for file)."""
+    import numpy as np
+    import torch
+    out = torch.arange(5 * 6 * 7 * 3, dtype=torch.float32).reshape(5, 6, 7, 3)
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    bench.dump_outputs(str(tmp_path / "b"), out)
+    a = {n: np.load(tmp_path / "a" / n) for n in sorted(os.listdir(tmp_path / "a"))}
+    assert list(a) == ["frames.npy", "frames_sample.npy"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert np.array_equal(a["frames.npy"], out[[0, 2, 4]].numpy())
+    assert a["frames_sample.npy"].shape == (out.numel(),) and np.isin(a["frames_sample.npy"], out.numpy()).all()
+    assert len(np.unique(a["frames_sample.npy"])) > out.numel() // 4
+    for n, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / n))
+    # config 4's step (125 x 1024 x 1024 x 3): the selection stays under the 64 MB limit
+    assert (bench.DUMP_VIEWS * 1024 * 1024 * 3 + bench.DUMP_SAMPLE) * 4 <= 64 * 10**6
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_its_frames(dev, tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` alone: one JSON line with the headline fields and
+    ms_per_step over exactly N steps, no other leg run; --dump-outputs leaves float32 arrays whose
+    seeded sample agrees with the whole frames (2 views per step: both are dumped whole)."""
+    import json
+    import numpy as np
+    import torch
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--views", "2", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-800:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 4096
+    line = json.loads(lines[0])
+    assert line["metric"] == bench.METRIC and line["unit"] == "Mpix/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f32" and line["steps"] == 3 and line["warmup"] == 1
+    assert line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(2 * 1024 * 1024 / 1e6 / (line["ms_per_step"] * 1e-3), rel=5e-3)  # (both rounded)
+    for leg in ("timed_frame_check", "cpu_baseline", "config2", "config3_psv", "notebook", "u8_texels",
+                "net_output_render", "training_render_backward", "config5_plane_sharded"):
+        assert line[leg] is None, leg
+    assert line["roofline"]["peak"] is None and line["roofline"]["single_view"] is None
+    frames, sample = np.load(d / "frames.npy"), np.load(d / "frames_sample.npy")
+    assert frames.dtype == np.float32 and frames.shape == (2, 1024, 1024, 3) and np.isfinite(frames).all()
+    assert frames.std() > 0.01
+    idx = torch.randint(0, frames.size, (bench.DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).numpy()
+    assert sample.dtype == np.float32 and np.array_equal(sample, frames.reshape(-1)[idx])
 
 
 def test_spawn_ranks_runs_torchrun_child(monkeypatch):

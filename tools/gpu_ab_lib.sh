@@ -18,7 +18,7 @@ done
 for so in build/ab_*.so; do
   n=$(basename $so .so)
   for v in ${VIEWS:-125 8 1}; do
-    MPIV_LIB=$(pwd)/$so timeout -k 10 180 python -u bench.py --views $v --steps 5 --warmup 1 --cpu-seconds 0 > $OUT/${n}_b$v.log 2>&1 \
+    MPIV_LIB=$(pwd)/$so timeout -k 10 180 python -u bench.py --full --views $v --steps 5 --warmup 1 --cpu-seconds 0 > $OUT/${n}_b$v.log 2>&1 \
       || { echo "$n bench failed"; tail -3 $OUT/${n}_b$v.log; exit 1; }
     python -c "
 import json

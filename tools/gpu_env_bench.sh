@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out; mkdir -p $OUT
 for e in ${ENVS}; do
   for v in ${VIEWS:-125 8 1}; do
-    env $e timeout -k 10 180 python -u bench.py --views $v --steps 5 --warmup 1 --cpu-seconds 0 > $OUT/eb_${e}_$v.log 2>&1 \
+    env $e timeout -k 10 180 python -u bench.py --full --views $v --steps 5 --warmup 1 --cpu-seconds 0 > $OUT/eb_${e}_$v.log 2>&1 \
       || { echo "$e $v failed"; tail -3 $OUT/eb_${e}_$v.log; exit 1; }
     python -c "
 import json

@@ -10,10 +10,10 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/gpu_tests_$TAG.log 2>&1
   rc=$?; echo "tests rc=$rc"; tail -3 $OUT/gpu_tests_$TAG.log; [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 400 python3 -u bench.py ${BENCH_ARGS:-} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout -k 10 400 python3 -u bench.py --full ${BENCH_ARGS:-} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 rc=$?; echo "bench rc=$rc"; tail -c 400 $OUT/bench_$TAG.err; [ $rc -eq 0 ] || exit $rc
 if [ "${SKIP_MULTI:-0}" != 1 ]; then
-  MPIV_BENCH_BACKEND=gloo MPIV_BENCH_ONE_DEVICE=1 timeout -k 10 400 python3 -u bench.py --gpus 2 --steps 3 --warmup 1 \
+  MPIV_BENCH_BACKEND=gloo MPIV_BENCH_ONE_DEVICE=1 timeout -k 10 400 python3 -u bench.py --full --gpus 2 --steps 3 --warmup 1 \
       --cpu-seconds 0 > $OUT/bench2_$TAG.json 2> $OUT/bench2_$TAG.err
   rc=$?; echo "bench --gpus 2 rc=$rc"; tail -c 400 $OUT/bench2_$TAG.err; [ $rc -eq 0 ] || exit $rc
 fi

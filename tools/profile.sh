@@ -12,8 +12,8 @@ OUT=$ROOT/gpurun_out/prof
 # the trace pass runs the driver's own bench command (--steps 20 --warmup 5), so every timed leg
 # has as many dispatches in the summary as in the driver's line; the counter passes only need the
 # per-dispatch shapes and stay short
-TRACE_ARGS=${PROF_TRACE_ARGS:---steps 20 --warmup 5 --cpu-seconds 0}
-ARGS=${PROF_ARGS:---steps 3 --warmup 1 --cpu-seconds 0}
+TRACE_ARGS=${PROF_TRACE_ARGS:---full --steps 20 --warmup 5 --cpu-seconds 0}
+ARGS=${PROF_ARGS:---full --steps 3 --warmup 1 --cpu-seconds 0}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run \
