@@ -124,6 +124,10 @@ inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / p
 //   render_same=-1|0|1|2  render_rows_kernel's same-row tap reuse (render.hip SAME): off / automatic
 //                      (where the sample advances <= 0.8 texel rows per output row; R = 6 then, with
 //                      OOB for launches of <= 2 views) / on / on with OOB
+//   render_colsep=-1|0|1  the rows kernels' column-separable issue path (render.hip ColSet: views whose
+//                      planes all have h[1] == h[7] == 0 compute the u, w chain and everything derived
+//                      from it once per column and plane): off / automatic (the kernel tests the view's
+//                      homographies) / test hook: taken without the test (wrong bits on other views)
 //   bwd_margin=k       the tile gather's pixel-window margin in 1/64 pixel (default 16);
 //                      negative values make windows miss contributors, which the pair
 //                      count must catch (tests)
@@ -134,7 +138,7 @@ enum DebugOpt { kOptRenderMv, kOptRenderPair, kOptNativeLds, kOptSweepTile, kOpt
                 kOptRenderVshare, kOptChunkRows, kOptSweepRows, kOptChunkFlight, kOptBwdGather, kOptSweepDirect,
                 kOptBwdPollLimit, kOptBwdFbBlocks, kOptBwdFbMode, kOptChunkStrip, kOptU8Flight, kOptBwdGroup,
                 kOptNetoutGeo, kOptNetoutBuf, kOptBwdOverlap, kOptSweepBand, kOptSweepPf, kOptSweepSoa, kOptBwdUnfold,
-                kOptNetoutFg3, kOptRenderSame, kNumOpts };
+                kOptNetoutFg3, kOptRenderSame, kOptRenderColsep, kNumOpts };
 const char* const kOptNames[kNumOpts] = {"render_mv", "render_pair", "render_native_lds",
                                          "sweep_tile", "sweep_store", "box_shrink", "render_chunk", "render_ring",
                                          "render_tile", "bwd_fallback", "bwd_margin", "sweep_dlane",
@@ -142,7 +146,7 @@ const char* const kOptNames[kNumOpts] = {"render_mv", "render_pair", "render_nat
                                          "sweep_direct", "bwd_poll_limit", "bwd_fb_blocks", "bwd_fb_mode",
                                          "chunk_strip", "u8_flight", "bwd_group", "netout_geo", "netout_buf", "bwd_overlap", "sweep_band",
                                          "sweep_pf", "sweep_soa", "bwd_unfold", "netout_fg3",
-                                         "render_same"};
+                                         "render_same", "render_colsep"};
 #ifndef MPIV_CHUNK_STRIP
 #define MPIV_CHUNK_STRIP 1  // round 4: 0.506 vs 0.64 ms in place (profiles/r04j_strip*_ab.jsonl)
 #endif
@@ -150,9 +154,9 @@ const char* const kOptNames[kNumOpts] = {"render_mv", "render_pair", "render_nat
 #define MPIV_U8_FLIGHT 0
 #endif
 const int kOptDefaults[kNumOpts] = {0, 0, 1, 0, -1, 0, 0, 0, 0, 0, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, MPIV_CHUNK_STRIP,
-                                    MPIV_U8_FLIGHT, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0};
+                                    MPIV_U8_FLIGHT, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0};
 int g_opts[kNumOpts] = {0, 0, 1, 0, -1, 0, 0, 0, 0, 0, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, MPIV_CHUNK_STRIP, MPIV_U8_FLIGHT, 0,
-                        0, 1, 0, 0, 0, 0, 0, 1, 0};
+                        0, 1, 0, 0, 0, 0, 0, 1, 0, 0};
 
 int opt(DebugOpt o) { return __atomic_load_n(&g_opts[o], __ATOMIC_RELAXED); }
 
@@ -499,7 +503,12 @@ static int render_packed_impl(const float* packed, int H, int W, int P, int p_be
     //  * round 6: where the sample advances <= 0.8 texel rows per output row (configs 2 and 5),
     //    same-row tap reuse with R = 6, D = 3 at every view count (profiles/r06_same_ab*.jsonl:
     //    config-5 shard 0.655-0.67 vs 0.77-0.78 ms, config 2 at 64 views 1.95-1.96 vs 2.05, at
-    //    8 views 0.253-0.256 vs 0.26-0.27).
+    //    8 views 0.253-0.256 vs 0.26-0.27);
+    //  * round 7: every flavour below tests its view's homographies in the kernel and takes the
+    //    column-separable issue path where h[1] == h[7] == 0 on every plane (render.hip ColSet;
+    //    render_colsep=-1 turns it off): config 4 at 125 views 25.9 -> 23.5 ms.  With that path (9, 3)
+    //    measured 23.3 ms against (6, 3)'s 23.66, without it 26.08 against 25.94: the host cannot tell
+    //    which a launch will take, so near-square MPIs keep (6, 3) (profiles/r07_colsep.json).
     const float sxr = (float)W / (float)(H > 1 ? H - 1 : 1), syr = (float)H / (float)(W > 1 ? W - 1 : 1);
     const bool square = sxr >= 0.8f && sxr <= 1.25f && syr >= 0.8f && syr <= 1.25f;
     const int rows_opt = opt(kOptRenderTile);
@@ -549,17 +558,18 @@ static int render_packed_impl(const float* packed, int H, int W, int P, int p_be
                               vsd == 3 || vsd == 11 ? 4 : 3, same ? "true" : "false", oob ? "true" : "false");
         unsigned long long* cn = (g_census && !ct) ? g_census : nullptr;
         if (cn) g_census = nullptr;
+        const int csp = opt(kOptRenderColsep);  // the column-separable issue path (render.hip ColSet)
 #define MPIV_VSD(R, D, SM, OB)                                                                                        \
     if (ct)                                                                                                          \
-        render_rows_kernel<true, R, true, false, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(pk, ps, g, V, p_begin,     \
-                                                                                           p_end, back, homs, out);  \
+        render_rows_kernel<true, R, true, false, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(                           \
+            pk, ps, g, V, p_begin, p_end, back, homs, out, nullptr, 0, -1, csp);                                     \
     else                                                                                                             \
-        render_rows_kernel<false, R, true, false, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(pk, ps, g, V, p_begin,    \
-                                                                                            p_end, 1, homs, out)
+        render_rows_kernel<false, R, true, false, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(                          \
+            pk, ps, g, V, p_begin, p_end, 1, homs, out, nullptr, 0, -1, csp)
 #define MPIV_VSDC(R, D, SM, OB)                                                                                       \
     if (cn)                                                                                                          \
-        render_rows_kernel<false, R, true, true, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(pk, ps, g, V, p_begin,     \
-                                                                                          p_end, 1, homs, out, cn);  \
+        render_rows_kernel<false, R, true, true, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(                           \
+            pk, ps, g, V, p_begin, p_end, 1, homs, out, cn, 0, -1, csp);                                             \
     else                                                                                                             \
         MPIV_VSD(R, D, SM, OB)
         if (oob) {
@@ -598,19 +608,19 @@ static int render_packed_impl(const float* packed, int H, int W, int P, int p_be
         else if (rows == 8 && g_census && !ct) {  // the counting build (mpiv_render_packed_census)
             unsigned long long* cn = g_census;
             g_census = nullptr;
-            if (vs)
+            if (vs)  // the A/B kernels keep the plain issue path (colsep = -1)
                 render_rows_kernel<false, 8, true, true><<<(unsigned)nb, 256, 0, st>>>(pk, ps, g, V, p_begin, p_end, 1,
-                                                                                       homs, out, cn);
+                                                                                       homs, out, cn, 0, -1, -1);
             else
                 render_rows_kernel<false, 8, false, true><<<(unsigned)nb, 256, 0, st>>>(pk, ps, g, V, p_begin, p_end,
                                                                                         1, homs, out, cn);
         } else if (rows == 8 && vs) {
             if (ct)
                 render_rows_kernel<true, 8, true><<<(unsigned)nb, 256, 0, st>>>(pk, ps, g, V, p_begin, p_end, back, homs,
-                                                                                 out);
+                                                                                 out, nullptr, 0, -1, -1);
             else
                 render_rows_kernel<false, 8, true><<<(unsigned)nb, 256, 0, st>>>(pk, ps, g, V, p_begin, p_end, 1, homs,
-                                                                                  out);
+                                                                                  out, nullptr, 0, -1, -1);
         } else if (rows == 8) MPIV_ROWS(8);
         else MPIV_ROWS(16);
 #undef MPIV_ROWS
@@ -693,12 +703,13 @@ int mpiv_render_packed_ct_rows(const float* packed, int H, int W, int P, int p_b
         return note_route(nb, 256, "render_rows_kernel<true, %d, true, false, %d, %s, %s>", R, R == 4 || R == 8 ? 4 : 3,
                           same ? "true" : "false", oob ? "true" : "false");
     hipStream_t st = S(stream);
+    const int csp = opt(kOptRenderColsep);
 #define MPIV_CTR(RR, DD, SM)                                                                                           \
     render_rows_kernel<true, RR, true, false, DD, SM><<<(unsigned)nb, 256, 0, st>>>(pk, ps, g, V, p_begin, p_end, back, \
-                                                                                    homs, ct, nullptr, y_begin, y_end)
+                                                                                    homs, ct, nullptr, y_begin, y_end, csp)
     if (oob) {
         render_rows_kernel<true, 6, true, false, 3, true, true><<<(unsigned)nb, 256, 0, st>>>(
-            pk, ps, g, V, p_begin, p_end, back, homs, ct, nullptr, y_begin, y_end);
+            pk, ps, g, V, p_begin, p_end, back, homs, ct, nullptr, y_begin, y_end, csp);
     } else if (same) {
         switch (R) {
             case 4: MPIV_CTR(4, 4, true); break;
@@ -1993,9 +2004,10 @@ static int render_u8_impl(const uint32_t* packed, int H, int W, int P, int p_beg
     }
     const unsigned* pk = reinterpret_cast<const unsigned*>(packed);
     hipStream_t q = S(stream);
+    const int csp = opt(kOptRenderColsep);  // the column-separable issue path (render.hip ColSet)
 #define MPIV_U8(CT, RR, VV)                                                                                       \
     render_u8_kernel<CT, RR, VV><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, CT ? back : 1, \
-                                                              homs, out)
+                                                              homs, out, csp)
 #if MPIV_AB  // 8 rows per work-item (A/B)
     if (R == 8) {
         if (vs && ct) MPIV_U8(true, 8, true);
@@ -2010,14 +2022,14 @@ static int render_u8_impl(const uint32_t* packed, int H, int W, int P, int p_beg
     const int u8f = opt(kOptU8Flight) ? opt(kOptU8Flight) : (nb < 2048 ? 4 : 2);
     if (vs && u8f == 8) {  // 8 rows in flight (two planes' rows)
         if (ct) render_u8_kernel<true, 4, true, 8><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, back,
-                                                                              homs, out);
+                                                                              homs, out, csp);
         else render_u8_kernel<false, 4, true, 8><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, 1,
-                                                                             homs, out);
+                                                                             homs, out, csp);
     } else if (vs && u8f == 4) {  // 4 rows in flight
         if (ct) render_u8_kernel<true, 4, true, 4><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, back,
-                                                                              homs, out);
+                                                                              homs, out, csp);
         else render_u8_kernel<false, 4, true, 4><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, 1,
-                                                                             homs, out);
+                                                                             homs, out, csp);
     } else if (vs) {
         if (ct) MPIV_U8(true, 4, true);
         else MPIV_U8(false, 4, true);

@@ -102,6 +102,48 @@ __device__ __forceinline__ void render_pos_fast(const float* __restrict__ h, flo
     py = unnormalize(to_grid(cy), g.half_h);
 }
 
+// COLUMN-SEPARABLE planes (round 7).  A camera that yaws and translates but neither pitches nor
+// rolls gives homographies with h[1] == h[7] == +-0 (the reference's K (R^T + R^T t n^T R^T / d) K^-1
+// with zero skew: sway, stereo and light-field baselines, turntables).  Then u = fma(h1, fy, RN(h0*fx))
+// + h2 and w = fma(h7, fy, RN(h6*fx)) + h8 are the same bits for every row fy >= 0 of a column: +-0 * fy
+// is one signed zero for all finite fy >= 0, and adding it to a fixed value gives a fixed result (the
+// signed-zero sums included).  Everything render_pos_fast and the tap setup derive from u and w alone
+// -- the refined reciprocal of w, qu, px, floor(px), the x weights and the clamped tap column -- is
+// then computed once per (lane, plane) at the lane's first row, with the same expressions (the same
+// bits), and the rows run only the v chain: ~23 of a continuing row's ~87 VALU.
+struct ColSet {
+    float w, y;    // w and its refined reciprocal (div2_fast)
+    float wx, ex;  // issue_taps_padded's x weights
+    int coff;      // byte offset of the clamped tap column: cx * TEXEL + org
+};
+
+// TEXEL: bytes per texel (16: float4 planes, 4: packed u8)
+template <int TEXEL>
+__device__ __forceinline__ ColSet col_setup(const float* __restrict__ h, float fx, float fy, const RenderGeom& g,
+                                            int org) {
+    ColSet c;
+    const float u = __builtin_fmaf(h[1], fy, h[0] * fx) + h[2];
+    c.w = __builtin_fmaf(h[7], fy, h[6] * fx) + h[8];
+    float y = __builtin_amdgcn_rcpf(c.w);
+    const float e = __builtin_fmaf(-c.w, y, 1.0f);
+    c.y = __builtin_fmaf(e, y, y);
+    const float qu = div_core(u, c.w, c.y);
+    const float px = unnormalize(to_grid(div_const(qu, g.hm1, g.rc_hm1)), g.half_w);
+    const float fx0 = floorf(px);
+    c.wx = px - fx0;
+    c.ex = 1.0f - c.wx;
+    c.coff = (int)__builtin_amdgcn_fmed3f(fx0, -2.0f, (float)g.W) * TEXEL + org;
+    return c;
+}
+
+// render_pos_fast<false>'s py for row fy of a column whose u, w chain is in c
+__device__ __forceinline__ float col_row_py(const float* __restrict__ h, float fx, float fy, const ColSet& c,
+                                            const RenderGeom& g) {
+    const float v = __builtin_fmaf(h[4], fy, h[3] * fx) + h[5];
+    const float qv = div_core(v, c.w, c.y);
+    return unnormalize(to_grid(div_const(qv, g.wm1, g.rc_wm1)), g.half_h);
+}
+
 // True when div2_safe(u, v, w) holds for every pixel of [x0, x1] x [y0, y1] (integer
 // coordinates).  Each computed coordinate, e.g. u = fma(h1, y, RN(h0*x)) + h2, is a chain
 // of correctly rounded operations that are each monotone in x (direction: sign of h0)
@@ -423,7 +465,11 @@ __device__ __forceinline__ void render_rows_pixels(const float4* __restrict__ pl
 // memory words).  Per row and wave the south pair is gathered as before and the north pair only when
 // some lane neither stayed nor moved one row down (a lane that stayed keeps the previous row's north
 // taps): 2 gathers per row instead of 4 on most rows of a stretched frame.
-template <bool CT, bool GUARD, int R, int D = 2, bool SAME = false, bool OOB = false>
+// CS (round 7): every plane of the view is column-separable (ColSet above; the kernel's prologue
+// tests h[1] == h[7] == 0 for the block's view): the column set is computed at the first row a
+// plane issues and is live at issue time only (the weights travel in RowTaps), so the ring, which
+// issues rows of plane p + 1 while plane p blends, holds one set, not two.
+template <bool CT, bool GUARD, int R, int D = 2, bool SAME = false, bool OOB = false, bool CS = false>
 __device__ __forceinline__ void render_rows_vs_pixels(const float4* __restrict__ planes, int64_t plane_stride,
                                                       const RenderGeom& g, int p_begin, int p_end, int back,
                                                       const float* __restrict__ hv, int x, int y0,
@@ -445,21 +491,37 @@ __device__ __forceinline__ void render_rows_vs_pixels(const float4* __restrict__
     const bool replace_first = !CT || back;
     const int last = p_end - 1;
     auto hom = [&](int p) { return load_hom(hv + (int64_t)(p < last ? p : last) * 9); };
+    static_assert(!CS || !GUARD, "the column set shares one proven division");
+    [[maybe_unused]] ColSet col;  // CS: the plane being issued (can_share is false at a plane's first row)
     auto issue = [&](int p, int k, const Hom9& h, int prev_off, bool can_share, RowTaps& t) {
         const int q = p < last ? p : last;
-        float px, py;
-        render_pos_fast<GUARD>(h.h, fx, (float)(y0 + k), g, px, py);
+        float py, wx, ex;
+        int off;
+        if constexpr (CS) {
+            if (!can_share) col = col_setup<16>(h.h, fx, (float)y0, g, g.org);
+            py = col_row_py(h.h, fx, (float)(y0 + k), col, g);
+            wx = col.wx;
+            ex = col.ex;
+        } else {
+            float px;
+            render_pos_fast<GUARD>(h.h, fx, (float)(y0 + k), g, px, py);
+            const float fx0 = floorf(px);
+            wx = px - fx0;
+            ex = 1.0f - wx;
+            off = (int)__builtin_amdgcn_fmed3f(fx0, -2.0f, (float)g.W);  // cx
+        }
         // issue_taps_padded's weights and clamped offset
-        const float fx0 = floorf(px), fy0 = floorf(py);
-        const float wx = px - fx0, ex = 1.0f - wx;
+        const float fy0 = floorf(py);
         const float wy = py - fy0, sy = 1.0f - wy;
         t.nw = sy * ex;
         t.ne = sy * wx;
         t.sw = wy * ex;
         t.se = wy * wx;
-        const int cx = (int)__builtin_amdgcn_fmed3f(fx0, -2.0f, (float)g.W);
         const int cy = (int)__builtin_amdgcn_fmed3f(fy0, -2.0f, (float)g.H);
-        const int off = (__mul24(cy, g.Wp) + cx) * 16 + g.org;
+        if constexpr (CS)
+            off = __mul24(cy, g.Wp) * 16 + col.coff;  // the same integer: (cy*Wp + cx)*16 + org
+        else
+            off = (__mul24(cy, g.Wp) + off) * 16 + g.org;
         t.off = off;
         t.sh = can_share && off == prev_off + g.row;
         const __amdgpu_buffer_rsrc_t r = make_rsrc(planes + (int64_t)q * plane_stride, g.plane_bytes);
@@ -745,7 +807,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAME && R =
                                                           RenderGeom g, int V, int p_begin, int p_end, int back,
                                                           const float* __restrict__ homs, float* __restrict__ out,
                                                           unsigned long long* __restrict__ census = nullptr,
-                                                          int y_lo = 0, int y_hi = -1) {
+                                                          int y_lo = 0, int y_hi = -1, int colsep = 0) {
     constexpr int TY = 4 * R;
     if (y_hi < 0) y_hi = g.H;
     const int tiles_x = (g.W + kTileX - 1) / kTileX;
@@ -756,7 +818,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAME && R =
     const int x = tx0 + (int)(threadIdx.x & (kWave - 1));
     const int y0 = ty0 + (int)(threadIdx.x >> 6) * R;
     const float* hv = homs + (int64_t)v * g.P * 9;
-    bool ok = true, dd = true;
+    bool ok = true, dd = true, cs = true;
     {
         const float x0 = (float)tx0, x1 = (float)min(tx0 + kTileX - 1, g.W - 1);
         const float fy0 = (float)ty0, fy1 = (float)min(ty0 + TY - 1, g.H - 1);
@@ -765,10 +827,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAME && R =
             const bool safe = div2_rect_safe(hp, x0, x1, fy0, fy1);
             ok = ok && safe;
             dd = dd && safe && tile_dead(hp, x0, x1, fy0, fy1, g);
+            cs = cs && hp[1] == 0.0f && hp[7] == 0.0f;  // both signed zeros; NaN fails
         }
     }
     const bool proven = __syncthreads_and(ok);
     const bool dead = __syncthreads_and(dd);
+    // column-separable view (ColSet): every plane of the range has h[1] == h[7] == 0.  colsep (the
+    // render_colsep option): 0 automatic, -1 never, 1 without the test (a test hook)
+    // (the (C, T) same-row flavour with R = 8, reached through debug options only, keeps the row
+    // recipe: with both row loops it spills two SGPRs)
+    constexpr bool COLSEP = VS && !(CT && SAME && R == 8);
+    bool sep = false;
+    if constexpr (COLSEP) sep = colsep > 0 || (colsep == 0 && __syncthreads_and(cs));
     if (x >= g.W || y0 >= y_hi) return;  // rows past y_hi inside [y0, y0+R) are computed, not stored
     float cr[R], cg[R], cb[R], tt[R];
 #pragma unroll
@@ -793,29 +863,41 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAME && R =
             atomicAdd(census, (unsigned long long)rows * 4ull * (unsigned long long)(p_end - p_begin + 1));
         return;
     }
+    auto store = [&]() {
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            const int y = y0 + k;
+            if (y >= y_hi) break;
+            const int64_t o = ((int64_t)v * g.H + y) * g.W + x;
+            if (CT) {
+                reinterpret_cast<float4*>(out)[o] = make_float4(cr[k], cg[k], cb[k], tt[k]);
+            } else {
+                out[o * 3 + 0] = cr[k];
+                out[o * 3 + 1] = cg[k];
+                out[o * 3 + 2] = cb[k];
+            }
+        }
+    };
     if (!dead) {
         unsigned nvm = 0;
-        if constexpr (VS)
+        if constexpr (VS) {
+            if (COLSEP && sep) {  // block-uniform
+                render_rows_vs_pixels<CT, false, R, D, SAME, OOB, COLSEP>(planes, plane_stride, g, p_begin, p_end, back, hv,
+                                                                        x, y0, cr, cg, cb, tt, nvm);
+                if (COUNT && (threadIdx.x & (kWave - 1)) == 0) atomicAdd(census, (unsigned long long)nvm);
+                // stored here: with the two row loops' results merged before one store loop, the R
+                // rows' colours stay live twice (3R more VGPRs, a wave per SIMD lost)
+                store();
+                return;
+            }
             render_rows_vs_pixels<CT, false, R, D, SAME, OOB>(planes, plane_stride, g, p_begin, p_end, back, hv, x, y0, cr,
-                                                         cg, cb, tt, nvm);
-        else  // 4 gathers per issue: R per plane plus the first
+                                                              cg, cb, tt, nvm);
+        } else  // 4 gathers per issue: R per plane plus the first
             render_rows_pixels<CT, false, R>(planes, plane_stride, g, p_begin, p_end, back, hv, x, y0, cr, cg, cb, tt);
         if (!VS) nvm = 4u * (unsigned)(R * (p_end - p_begin) + 1);
         if (COUNT && (threadIdx.x & (kWave - 1)) == 0) atomicAdd(census, (unsigned long long)nvm);
     }
-#pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int y = y0 + k;
-        if (y >= y_hi) break;
-        const int64_t o = ((int64_t)v * g.H + y) * g.W + x;
-        if (CT) {
-            reinterpret_cast<float4*>(out)[o] = make_float4(cr[k], cg[k], cb[k], tt[k]);
-        } else {
-            out[o * 3 + 0] = cr[k];
-            out[o * 3 + 1] = cg[k];
-            out[o * 3 + 2] = cb[k];
-        }
-    }
+    store();
 }
 
 // ---------------------------------------------------------------------------

@@ -127,7 +127,9 @@ __device__ __forceinline__ void render_u8_pixels(const unsigned* __restrict__ pl
 // D > 2: a ring of D rows in flight (row k + D - 1 issued while row k blends, running on into the
 // next planes; the plane loop is unrolled by D / R when D > R so ring positions stay static).  At one view the launch has
 // 4 waves per SIMD (R = 4), so the loads each wave keeps in flight are what hides HBM latency.
-template <bool CT, bool GUARD, int R, int D = 2>
+// CS: a column-separable view (render.hip ColSet): px, the x weight and the tap column once per
+// plane, at the first row the plane issues.
+template <bool CT, bool GUARD, int R, int D = 2, bool CS = false>
 __device__ __forceinline__ void render_u8_vs_pixels(const unsigned* __restrict__ planes, int64_t plane_stride,
                                                     const RenderGeom& g, const U8Geom& ug, int p_begin, int p_end,
                                                     int back, const float* __restrict__ hv, int x, int y0, float* cr,
@@ -143,16 +145,30 @@ __device__ __forceinline__ void render_u8_vs_pixels(const unsigned* __restrict__
     const bool replace_first = !CT || back;
     const int last = p_end - 1;
     auto hom = [&](int p) { return load_hom(hv + (int64_t)(p < last ? p : last) * 9); };
+    static_assert(!CS || !GUARD, "the column set shares one proven division");
+    [[maybe_unused]] ColSet col;  // CS: the plane being issued (can_share is false at a plane's first row)
     auto issue = [&](int p, int k, const Hom9& h, int prev_off, bool can_share, RowU8& t) {
         const int q = p < last ? p : last;
-        float px, py;
-        render_pos_fast<GUARD>(h.h, fx, (float)(y0 + k), g, px, py);
-        const float fx0 = floorf(px), fy0 = floorf(py);
-        t.wx = px - fx0;
+        float py;
+        int off;
+        if constexpr (CS) {
+            if (!can_share) col = col_setup<4>(h.h, fx, (float)y0, g, ug.org);
+            py = col_row_py(h.h, fx, (float)(y0 + k), col, g);
+            t.wx = col.wx;
+        } else {
+            float px;
+            render_pos_fast<GUARD>(h.h, fx, (float)(y0 + k), g, px, py);
+            const float fx0 = floorf(px);
+            t.wx = px - fx0;
+            off = (int)__builtin_amdgcn_fmed3f(fx0, -2.0f, (float)g.W);  // cx
+        }
+        const float fy0 = floorf(py);
         t.wy = py - fy0;
-        const int cx = (int)__builtin_amdgcn_fmed3f(fx0, -2.0f, (float)g.W);
         const int cy = (int)__builtin_amdgcn_fmed3f(fy0, -2.0f, (float)g.H);
-        const int off = (__mul24(cy, g.Wp) + cx) * 4 + ug.org;
+        if constexpr (CS)
+            off = __mul24(cy, g.Wp) * 4 + col.coff;  // the same integer: (cy*Wp + cx)*4 + org
+        else
+            off = (__mul24(cy, g.Wp) + off) * 4 + ug.org;
         t.off = off;
         t.sh = can_share && off == prev_off + ug.row;
         const __amdgpu_buffer_rsrc_t r = make_rsrc(planes + (int64_t)q * plane_stride, ug.plane_bytes);
@@ -293,7 +309,7 @@ template <bool CT, int R, bool VS = false, int D = 2>
 __global__ __launch_bounds__(256) void render_u8_kernel(const unsigned* __restrict__ planes, int64_t plane_stride,
                                                         RenderGeom g, U8Geom ug, int V, int p_begin, int p_end,
                                                         int back, const float* __restrict__ homs,
-                                                        float* __restrict__ out) {
+                                                        float* __restrict__ out, int colsep = 0) {
     constexpr int TY = 4 * R;
     const int tiles_x = (g.W + kTileX - 1) / kTileX;
     const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
@@ -303,7 +319,7 @@ __global__ __launch_bounds__(256) void render_u8_kernel(const unsigned* __restri
     const int x = tx0 + (int)(threadIdx.x & (kWave - 1));
     const int y0 = ty0 + (int)(threadIdx.x >> 6) * R;
     const float* hv = homs + (int64_t)v * g.P * 9;
-    bool ok = true, dd = true;
+    bool ok = true, dd = true, cs = true;
     {
         const float x0 = (float)tx0, x1 = (float)min(tx0 + kTileX - 1, g.W - 1);
         const float fy0 = (float)ty0, fy1 = (float)min(ty0 + TY - 1, g.H - 1);
@@ -312,10 +328,14 @@ __global__ __launch_bounds__(256) void render_u8_kernel(const unsigned* __restri
             const bool safe = div2_rect_safe(hp, x0, x1, fy0, fy1);
             ok = ok && safe;
             dd = dd && safe && tile_dead(hp, x0, x1, fy0, fy1, g);
+            cs = cs && hp[1] == 0.0f && hp[7] == 0.0f;  // both signed zeros; NaN fails
         }
     }
     const bool proven = __syncthreads_and(ok);
     const bool dead = __syncthreads_and(dd);
+    // column-separable view (render.hip ColSet; colsep as render_rows_kernel's)
+    bool sep = false;
+    if constexpr (VS) sep = colsep > 0 || (colsep == 0 && __syncthreads_and(cs));
     if (x >= g.W || y0 >= g.H) return;  // rows past H inside [y0, y0+R) are computed, not stored
     float cr[R], cg[R], cb[R], tt[R];
 #pragma unroll
@@ -329,10 +349,14 @@ __global__ __launch_bounds__(256) void render_u8_kernel(const unsigned* __restri
             cr[k] = cr[0]; cg[k] = cg[0]; cb[k] = cb[0]; tt[k] = tt[0];
         }
     } else if (proven) {
-        if constexpr (VS)
-            render_u8_vs_pixels<CT, false, R, D>(planes, plane_stride, g, ug, p_begin, p_end, back, hv, x, y0, cr, cg,
-                                                 cb, tt);
-        else
+        if constexpr (VS) {
+            if (sep)  // block-uniform
+                render_u8_vs_pixels<CT, false, R, D, true>(planes, plane_stride, g, ug, p_begin, p_end, back, hv, x, y0,
+                                                           cr, cg, cb, tt);
+            else
+                render_u8_vs_pixels<CT, false, R, D>(planes, plane_stride, g, ug, p_begin, p_end, back, hv, x, y0, cr,
+                                                     cg, cb, tt);
+        } else
             render_u8_pixels<CT, false, R>(planes, plane_stride, g, ug, p_begin, p_end, back, hv, x, y0, cr, cg, cb,
                                            tt);
     } else {  // rare (w near 0 over the tile): the guarded recipe two rows at a time (few VGPRs)
