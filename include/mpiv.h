@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MPIV_ABI_VERSION 14
+#define MPIV_ABI_VERSION 15
 
 enum {
     MPIV_OK = 0,
@@ -421,6 +421,13 @@ int mpiv_unpack_planes_u8(const uint32_t *packed, int H, int W, int P, float *ou
 int mpiv_synth_mpi_packed_u8(uint32_t seed, int H, int W, int p_begin, int p_end, uint32_t *packed, void *stream);
 
 /* ---- diagnostics ------------------------------------------------------------ */
+
+/* The sampling kernels' tile order, on the host (no GPU; ntiles a multiple of tiles_x: whole tile
+ * rows): out[t] (ntiles entries) = the raster index
+ * ty * tiles_x + tx of the tile rendered at position t of the XCD-contiguous tile numbering, from the
+ * function the kernels use.  order -1: the band order (the identity); 1: the interleaved order (each
+ * XCD every eighth tile, the tile rows' columns rotated).  A permutation of [0, ntiles) either way. */
+int mpiv_tile_order(int ntiles, int tiles_x, int order, int32_t *out);
 
 /* Phase marker for profiles: launches an empty kernel of `tag` x 64 work-items (tag in 1..4096) on
  * the stream; tools/parse_prof.py files later dispatches under the last marker's tag. */

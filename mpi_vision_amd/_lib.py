@@ -86,11 +86,12 @@ _SIGS = {
     "mpiv_synth_mpi_packed": [ctypes.c_uint32, _int, _int, _int, _int, _vp, _vp],
     "mpiv_assemble_mpi_backward": [_vp, _c_i64p, _vp, _c_i64p, _vp, _c_i64p, _int, _int, _int, _int, _vp, _vp,
                                    _vp],
+    "mpiv_tile_order": [_int, _int, _int, ctypes.POINTER(ctypes.c_int32)],
 }
 EXPORTS = tuple(_SIGS) + ("mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
                           "mpiv_render_backward_abort_flag",
                           "mpiv_render_backward_workspace_size_min", "mpiv_build_id", "mpiv_debug_set")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _lib = None
 _lib_ab = None
@@ -277,6 +278,17 @@ def debug(**opts):
         yield
     finally:
         reset_debug()
+
+
+def tile_order(ntiles: int, tiles_x: int, order: int) -> list[int]:
+    """The sampling kernels' tile order on the host (mpiv_tile_order, no GPU needed): entry t is the
+    raster tile rendered at position t of the XCD-contiguous numbering; order -1 band, 1 interleaved."""
+    L = load_main()
+    out = (ctypes.c_int32 * max(ntiles, 1))()
+    rc = L.mpiv_tile_order(ntiles, tiles_x, order, out)
+    if rc != 0:
+        raise RuntimeError(f"mpiv_tile_order failed ({rc}): {L.mpiv_last_error().decode()}")
+    return list(out[:ntiles])
 
 
 def route(entry: str, *args: int) -> tuple[str, int]:

@@ -128,6 +128,9 @@ inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / p
 //                      planes all have h[1] == h[7] == 0 compute the u, w chain and everything derived
 //                      from it once per column and plane): off / automatic (the kernel tests the view's
 //                      homographies) / test hook: taken without the test (wrong bits on other views)
+//   render_order=-1|0|1  which tile a block of the sampling kernels (render_rows_kernel, render_u8_kernel,
+//                      render_packed_kernel) renders (render.hip xcd_tile_order): each XCD one band of tile
+//                      rows / automatic (render_tile_order) / every eighth tile, interleaved over the frame
 //   bwd_margin=k       the tile gather's pixel-window margin in 1/64 pixel (default 16);
 //                      negative values make windows miss contributors, which the pair
 //                      count must catch (tests)
@@ -138,7 +141,7 @@ enum DebugOpt { kOptRenderMv, kOptRenderPair, kOptNativeLds, kOptSweepTile, kOpt
                 kOptRenderVshare, kOptChunkRows, kOptSweepRows, kOptChunkFlight, kOptBwdGather, kOptSweepDirect,
                 kOptBwdPollLimit, kOptBwdFbBlocks, kOptBwdFbMode, kOptChunkStrip, kOptU8Flight, kOptBwdGroup,
                 kOptNetoutGeo, kOptNetoutBuf, kOptBwdOverlap, kOptSweepBand, kOptSweepPf, kOptSweepSoa, kOptBwdUnfold,
-                kOptNetoutFg3, kOptRenderSame, kOptRenderColsep, kNumOpts };
+                kOptNetoutFg3, kOptRenderSame, kOptRenderColsep, kOptRenderOrder, kNumOpts };
 const char* const kOptNames[kNumOpts] = {"render_mv", "render_pair", "render_native_lds",
                                          "sweep_tile", "sweep_store", "box_shrink", "render_chunk", "render_ring",
                                          "render_tile", "bwd_fallback", "bwd_margin", "sweep_dlane",
@@ -146,7 +149,7 @@ const char* const kOptNames[kNumOpts] = {"render_mv", "render_pair", "render_nat
                                          "sweep_direct", "bwd_poll_limit", "bwd_fb_blocks", "bwd_fb_mode",
                                          "chunk_strip", "u8_flight", "bwd_group", "netout_geo", "netout_buf", "bwd_overlap", "sweep_band",
                                          "sweep_pf", "sweep_soa", "bwd_unfold", "netout_fg3",
-                                         "render_same", "render_colsep"};
+                                         "render_same", "render_colsep", "render_order"};
 #ifndef MPIV_CHUNK_STRIP
 #define MPIV_CHUNK_STRIP 1  // round 4: 0.506 vs 0.64 ms in place (profiles/r04j_strip*_ab.jsonl)
 #endif
@@ -154,9 +157,9 @@ const char* const kOptNames[kNumOpts] = {"render_mv", "render_pair", "render_nat
 #define MPIV_U8_FLIGHT 0
 #endif
 const int kOptDefaults[kNumOpts] = {0, 0, 1, 0, -1, 0, 0, 0, 0, 0, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, MPIV_CHUNK_STRIP,
-                                    MPIV_U8_FLIGHT, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0};
+                                    MPIV_U8_FLIGHT, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0};
 int g_opts[kNumOpts] = {0, 0, 1, 0, -1, 0, 0, 0, 0, 0, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, MPIV_CHUNK_STRIP, MPIV_U8_FLIGHT, 0,
-                        0, 1, 0, 0, 0, 0, 0, 1, 0, 0};
+                        0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0};
 
 int opt(DebugOpt o) { return __atomic_load_n(&g_opts[o], __ATOMIC_RELAXED); }
 
@@ -217,6 +220,21 @@ constexpr int64_t kMaxGridX = 2147483647;
 using namespace mpiv;
 
 namespace {
+
+// The sampling kernels' tile order (render.hip xcd_tile_order) for a launch of V views: the
+// interleaved order (1) from kOrderMinViews views up, the band order (0) below.  With many views
+// an XCD's resident blocks are the views of one tile, so neighbouring tiles never met in its L2
+// anyway; a launch of fewer views runs neighbouring tiles at the same time on one XCD and they
+// share their halo lines, which the band order keeps.  render_order forces either.
+// Band / interleaved, ms (profiles/r08_order.json): config 4 at 8 views 2.12 / 2.32, 32 views
+// 6.87 / 7.17, 64 views 12.95 / 12.05, 125 views 24.36 / 22.67; config 2 at 8 views 0.153 / 0.171,
+// 32 views 0.562 / 0.576, 64 views 1.107 / 1.092 (a tie); the u8 kernel on config 4 at 8 views a
+// tie, at 32 views 6.89 / 6.57.
+constexpr int kOrderMinViews = 64;
+int render_tile_order(int V) {
+    const int o = opt(kOptRenderOrder);
+    return o > 0 ? 1 : o < 0 ? 0 : V >= kOrderMinViews ? 1 : 0;
+}
 
 // rows per wave of render_chunk_kernel (chunk_rows option; automatic: 1)
 int chunk_rows() {
@@ -559,17 +577,18 @@ static int render_packed_impl(const float* packed, int H, int W, int P, int p_be
         unsigned long long* cn = (g_census && !ct) ? g_census : nullptr;
         if (cn) g_census = nullptr;
         const int csp = opt(kOptRenderColsep);  // the column-separable issue path (render.hip ColSet)
+        const int ord = render_tile_order(V);
 #define MPIV_VSD(R, D, SM, OB)                                                                                        \
     if (ct)                                                                                                          \
         render_rows_kernel<true, R, true, false, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(                           \
-            pk, ps, g, V, p_begin, p_end, back, homs, out, nullptr, 0, -1, csp);                                     \
+            pk, ps, g, V, p_begin, p_end, back, homs, out, nullptr, 0, -1, csp, ord);                                \
     else                                                                                                             \
         render_rows_kernel<false, R, true, false, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(                          \
-            pk, ps, g, V, p_begin, p_end, 1, homs, out, nullptr, 0, -1, csp)
+            pk, ps, g, V, p_begin, p_end, 1, homs, out, nullptr, 0, -1, csp, ord)
 #define MPIV_VSDC(R, D, SM, OB)                                                                                       \
     if (cn)                                                                                                          \
         render_rows_kernel<false, R, true, true, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(                           \
-            pk, ps, g, V, p_begin, p_end, 1, homs, out, cn, 0, -1, csp);                                             \
+            pk, ps, g, V, p_begin, p_end, 1, homs, out, cn, 0, -1, csp, ord);                                        \
     else                                                                                                             \
         MPIV_VSD(R, D, SM, OB)
         if (oob) {
@@ -633,14 +652,15 @@ static int render_packed_impl(const float* packed, int H, int W, int P, int p_be
     const dim3 grid((unsigned)nblocks), blk(256);
     if (g_route)
         return note_route(nblocks, 256, "render_packed_kernel<%s, %s>", ct ? "true" : "false", fast ? "true" : "false");
+    const int ord = render_tile_order(V);
     if (ct && fast)
-        render_packed_kernel<true, true><<<grid, blk, 0, st>>>(pk, ps, g, V, p_begin, p_end, back, homs, out);
+        render_packed_kernel<true, true><<<grid, blk, 0, st>>>(pk, ps, g, V, p_begin, p_end, back, homs, out, ord);
     else if (ct)
-        render_packed_kernel<true, false><<<grid, blk, 0, st>>>(pk, ps, g, V, p_begin, p_end, back, homs, out);
+        render_packed_kernel<true, false><<<grid, blk, 0, st>>>(pk, ps, g, V, p_begin, p_end, back, homs, out, ord);
     else if (fast)
-        render_packed_kernel<false, true><<<grid, blk, 0, st>>>(pk, ps, g, V, p_begin, p_end, 1, homs, out);
+        render_packed_kernel<false, true><<<grid, blk, 0, st>>>(pk, ps, g, V, p_begin, p_end, 1, homs, out, ord);
     else
-        render_packed_kernel<false, false><<<grid, blk, 0, st>>>(pk, ps, g, V, p_begin, p_end, 1, homs, out);
+        render_packed_kernel<false, false><<<grid, blk, 0, st>>>(pk, ps, g, V, p_begin, p_end, 1, homs, out, ord);
     return launched(nm);
 }
 
@@ -704,12 +724,13 @@ int mpiv_render_packed_ct_rows(const float* packed, int H, int W, int P, int p_b
                           same ? "true" : "false", oob ? "true" : "false");
     hipStream_t st = S(stream);
     const int csp = opt(kOptRenderColsep);
+    const int ord = render_tile_order(V);
 #define MPIV_CTR(RR, DD, SM)                                                                                           \
     render_rows_kernel<true, RR, true, false, DD, SM><<<(unsigned)nb, 256, 0, st>>>(pk, ps, g, V, p_begin, p_end, back, \
-                                                                                    homs, ct, nullptr, y_begin, y_end, csp)
+                                                                                    homs, ct, nullptr, y_begin, y_end, csp, ord)
     if (oob) {
         render_rows_kernel<true, 6, true, false, 3, true, true><<<(unsigned)nb, 256, 0, st>>>(
-            pk, ps, g, V, p_begin, p_end, back, homs, ct, nullptr, y_begin, y_end, csp);
+            pk, ps, g, V, p_begin, p_end, back, homs, ct, nullptr, y_begin, y_end, csp, ord);
     } else if (same) {
         switch (R) {
             case 4: MPIV_CTR(4, 4, true); break;
@@ -2005,9 +2026,10 @@ static int render_u8_impl(const uint32_t* packed, int H, int W, int P, int p_beg
     const unsigned* pk = reinterpret_cast<const unsigned*>(packed);
     hipStream_t q = S(stream);
     const int csp = opt(kOptRenderColsep);  // the column-separable issue path (render.hip ColSet)
+    const int ord = render_tile_order(V);
 #define MPIV_U8(CT, RR, VV)                                                                                       \
     render_u8_kernel<CT, RR, VV><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, CT ? back : 1, \
-                                                              homs, out, csp)
+                                                              homs, out, csp, ord)
 #if MPIV_AB  // 8 rows per work-item (A/B)
     if (R == 8) {
         if (vs && ct) MPIV_U8(true, 8, true);
@@ -2022,14 +2044,14 @@ static int render_u8_impl(const uint32_t* packed, int H, int W, int P, int p_beg
     const int u8f = opt(kOptU8Flight) ? opt(kOptU8Flight) : (nb < 2048 ? 4 : 2);
     if (vs && u8f == 8) {  // 8 rows in flight (two planes' rows)
         if (ct) render_u8_kernel<true, 4, true, 8><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, back,
-                                                                              homs, out, csp);
+                                                                              homs, out, csp, ord);
         else render_u8_kernel<false, 4, true, 8><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, 1,
-                                                                             homs, out, csp);
+                                                                             homs, out, csp, ord);
     } else if (vs && u8f == 4) {  // 4 rows in flight
         if (ct) render_u8_kernel<true, 4, true, 4><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, back,
-                                                                              homs, out, csp);
+                                                                              homs, out, csp, ord);
         else render_u8_kernel<false, 4, true, 4><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, 1,
-                                                                             homs, out, csp);
+                                                                             homs, out, csp, ord);
     } else if (vs) {
         if (ct) MPIV_U8(true, 4, true);
         else MPIV_U8(false, 4, true);
@@ -2047,6 +2069,15 @@ int mpiv_render_packed_u8(const uint32_t* packed, int H, int W, int P, const flo
 int mpiv_render_packed_u8_ct(const uint32_t* packed, int H, int W, int P, int p_begin, int p_end, int back,
                              const float* homs, int V, float* ct, void* stream) {
     return render_u8_impl(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
+}
+
+int mpiv_tile_order(int ntiles, int tiles_x, int order, int32_t* out) {
+    if (!out) return fail(MPIV_ERR_ARG, "mpiv_tile_order: null pointer");
+    if (ntiles <= 0 || tiles_x <= 0 || ntiles % tiles_x)
+        return fail(MPIV_ERR_ARG, "mpiv_tile_order: bad shape (whole tile rows: ntiles a multiple of tiles_x)");
+    if (order != -1 && order != 1) return fail(MPIV_ERR_ARG, "mpiv_tile_order: order must be -1 (band) or 1 (interleaved)");
+    for (int t = 0; t < ntiles; ++t) out[t] = xcd_tile_order(t, ntiles, tiles_x, order);
+    return MPIV_OK;
 }
 
 int mpiv_mark(int tag, void* stream) {

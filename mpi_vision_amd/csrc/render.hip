@@ -253,12 +253,42 @@ __device__ __forceinline__ void composite_zero(int p_begin, int p_end, bool repl
 // logical id  start(b % 8) + b / 8, i.e. each XCD walks one contiguous range of
 // logical ids.  Logical ids enumerate (tile, view) with the VIEW fastest, so the
 // views of one output tile -- whose source footprints overlap almost entirely along a
-// camera path -- run together on one XCD and share its L2.  Placement only affects
-// speed, never correctness.
+// camera path -- run together on one XCD and share its L2.  Which tile a logical id's
+// tile position stands for is xcd_tile_order's business (the sampling kernels below; the
+// other kernels take the position as the raster tile).  Placement only affects speed,
+// never correctness.
 __device__ __forceinline__ int xcd_logical_block(int b, int nblocks) {
     const int q = nblocks >> 3, r = nblocks & 7;
     const int xcd = b & 7, k = b >> 3;
     return xcd * q + (xcd < r ? xcd : r) + k;
+}
+
+// The tile rendered at position t of the XCD-contiguous tile numbering (t = logical id / V).
+// order <= 0, the band order: the raster tile t, so each XCD renders one band of tile rows of
+// every view.  A band's cost follows its place in the frame (under yaw the rows at the top and
+// bottom issue their own north taps far more often than those at the principal row), and the
+// launch lasts as long as the dearest band's XCD.
+// order > 0, the interleaved order: position t lies in the range of XCD x = t / (ntiles / 8)
+// (the first ntiles % 8 ranges one longer) at offset k, and stands for the dealt tile
+// e = 8 k + x -- every eighth tile, so each XCD's tiles come from every tile row -- with the
+// tile row's columns rotated: by the row's index where tiles_x is a multiple of 8, so that the
+// XCD of tile (tx, ty) is (tx + ty) % 8 (without the rotation an XCD would own whole tile
+// columns, dead ones of a stretched MPI included).  For any tiles_x the dealt row ty starts at
+// XCD ty * tiles_x % 8, which walks the multiples of g = gcd(tiles_x, 8) with period 8 / g, so
+// one more step of rotation per period (ty * g / 8 in all) gives every XCD floor or ceil of an
+// eighth of each tile column as it has of each tile row.
+// A bijection of [0, ntiles) for ntiles a multiple of tiles_x >= 1 (whole tile rows).
+__host__ __device__ __forceinline__ int xcd_tile_order(int t, int ntiles, int tiles_x, int order) {
+    if (order <= 0) return t;
+    const int q = ntiles >> 3, r = ntiles & 7;
+    const int x = t < r * (q + 1) ? t / (q + 1) : r + (t - r * (q + 1)) / (q > 1 ? q : 1);
+    const int k = t - (x * q + (x < r ? x : r));
+    const int e = k * 8 + x;
+    const int ty = e / tiles_x;
+    const int g = (tiles_x | 8) & -(tiles_x | 8);  // gcd(tiles_x, 8)
+    const int rot = (int)(((int64_t)ty * g) >> 3);
+    const int tx = (e % tiles_x + tiles_x - rot % tiles_x) % tiles_x;
+    return ty * tiles_x + tx;
 }
 
 // CT = false: final colour [V,H,W,3]; plane p_begin is the back plane, whose alpha is
@@ -344,11 +374,11 @@ __global__ __launch_bounds__(256) void render_packed_kernel(const float4* __rest
                                                             int64_t plane_stride, RenderGeom g, int V,
                                                             int p_begin, int p_end, int back,
                                                             const float* __restrict__ homs,
-                                                            float* __restrict__ out) {
+                                                            float* __restrict__ out, int order = 0) {
     const int tiles_x = (g.W + kTileX - 1) / kTileX;
     const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
     const int v = lb % V;
-    const int tile = lb / V;
+    const int tile = xcd_tile_order(lb / V, (int)gridDim.x / V, tiles_x, order);
     const int tx0 = (tile % tiles_x) * kTileX, ty0 = (tile / tiles_x) * kTileY;
     const int x = tx0 + (threadIdx.x & (kWave - 1));
     const int y = ty0 + (threadIdx.x >> 6);
@@ -807,13 +837,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAME && R =
                                                           RenderGeom g, int V, int p_begin, int p_end, int back,
                                                           const float* __restrict__ homs, float* __restrict__ out,
                                                           unsigned long long* __restrict__ census = nullptr,
-                                                          int y_lo = 0, int y_hi = -1, int colsep = 0) {
+                                                          int y_lo = 0, int y_hi = -1, int colsep = 0,
+                                                          int order = 0) {
     constexpr int TY = 4 * R;
     if (y_hi < 0) y_hi = g.H;
     const int tiles_x = (g.W + kTileX - 1) / kTileX;
     const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
     const int v = lb % V;
-    const int tile = lb / V;
+    // the grid holds the tiles of rows [y_lo, y_hi) once per view (order: xcd_tile_order's)
+    const int tile = xcd_tile_order(lb / V, (int)gridDim.x / V, tiles_x, order);
     const int tx0 = (tile % tiles_x) * kTileX, ty0 = y_lo + (tile / tiles_x) * TY;
     const int x = tx0 + (int)(threadIdx.x & (kWave - 1));
     const int y0 = ty0 + (int)(threadIdx.x >> 6) * R;

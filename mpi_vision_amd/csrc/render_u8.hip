@@ -309,12 +309,13 @@ template <bool CT, int R, bool VS = false, int D = 2>
 __global__ __launch_bounds__(256) void render_u8_kernel(const unsigned* __restrict__ planes, int64_t plane_stride,
                                                         RenderGeom g, U8Geom ug, int V, int p_begin, int p_end,
                                                         int back, const float* __restrict__ homs,
-                                                        float* __restrict__ out, int colsep = 0) {
+                                                        float* __restrict__ out, int colsep = 0,
+                                                        int order = 0) {
     constexpr int TY = 4 * R;
     const int tiles_x = (g.W + kTileX - 1) / kTileX;
     const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
     const int v = lb % V;
-    const int tile = lb / V;
+    const int tile = xcd_tile_order(lb / V, (int)gridDim.x / V, tiles_x, order);  // render.hip
     const int tx0 = (tile % tiles_x) * kTileX, ty0 = (tile / tiles_x) * TY;
     const int x = tx0 + (int)(threadIdx.x & (kWave - 1));
     const int y0 = ty0 + (int)(threadIdx.x >> 6) * R;

@@ -63,7 +63,19 @@ int main() {
     EXPECT(mpiv_probe_gather(f, 16384, 0, 1, f, nullptr) == MPIV_ERR_ARG);
     EXPECT(mpiv_probe_gather(f, 4096, 1, 1, f, nullptr) == MPIV_ERR_ARG);
     EXPECT(mpiv_selftest_div_const(0, nullptr, nullptr) == MPIV_ERR_ARG);
+    // the tile order on an exact-size heap buffer: a permutation; bad arguments rejected
+    {
+        std::vector<int32_t> ord(9 * 5);
+        EXPECT(mpiv_tile_order(9 * 5, 9, 1, ord.data()) == MPIV_OK);
+        std::vector<int> seen(ord.size(), 0);
+        for (int32_t t : ord) EXPECT(t >= 0 && t < (int32_t)ord.size() && seen[t]++ == 0);
+        EXPECT(mpiv_tile_order(9 * 5, 9, -1, ord.data()) == MPIV_OK && ord[7] == 7);
+        EXPECT(mpiv_tile_order(10, 4, 1, ord.data()) == MPIV_ERR_ARG);
+        EXPECT(mpiv_tile_order(8, 4, 0, ord.data()) == MPIV_ERR_ARG);
+        EXPECT(mpiv_tile_order(8, 4, 1, nullptr) == MPIV_ERR_ARG);
+    }
     // debug options
+    EXPECT(mpiv_debug_set("render_order", 1) == MPIV_OK);
     EXPECT(mpiv_debug_set("render_mv", 1) == MPIV_OK);
     EXPECT(mpiv_debug_set("reset", 0) == MPIV_OK);
     EXPECT(mpiv_debug_set("nope", 1) == MPIV_ERR_ARG);
