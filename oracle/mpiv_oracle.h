@@ -27,6 +27,8 @@ void oracle_render_backward(const float *mpi, const int64_t st[5], int B, int H,
                             const float *homs, const float *dout, float *dmpi, int vec, int nthreads);
 /* layers [P][n][4] contiguous; out [n][3] */
 void oracle_over_composite(const float *layers, int P, int64_t n, float *out);
+/* parts [G][n][4] (C, T) partials ordered back -> front -> out [n][3] (combine_ct_kernel's recipe) */
+void oracle_combine_ct(const float *parts, int G, int64_t n, float *out);
 /* depth-map inverse warp: img [B,Hs,Ws,C] (strides), ki [B][9], proj [B][16],
  * depth [B][Ht][Wt] contiguous -> out [B,Ht,Wt,C] */
 void oracle_inverse_warp(const float *img, const int64_t st[4], int B, int Hs, int Ws, int C,

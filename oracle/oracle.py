@@ -37,6 +37,7 @@ def lib():
         L.oracle_grid_sample.argtypes = [_f, _i64] + [ctypes.c_int] * 4 + [_f, ctypes.c_int, ctypes.c_int,
                                                                           _f, _i64, ctypes.c_int]
         L.oracle_over_composite.argtypes = [_f, ctypes.c_int, ctypes.c_int64, _f]
+        L.oracle_combine_ct.argtypes = [_f, ctypes.c_int, ctypes.c_int64, _f]
         L.oracle_render_backward.argtypes = [_f, _i64] + [ctypes.c_int] * 4 + [_f, _f, _f, ctypes.c_int,
                                                                              ctypes.c_int]
         L.oracle_inverse_warp.argtypes = [_f, _i64] + [ctypes.c_int] * 4 + [_f, _f, _f, ctypes.c_int, ctypes.c_int,
@@ -101,13 +102,12 @@ def render_ct(mpi: np.ndarray, homs: np.ndarray, p0: int, p1: int, back: bool, n
 
 
 def combine_ct(parts: np.ndarray) -> np.ndarray:
-    """parts [G, ..., 4] ordered back->front -> [..., 3]: (Cf,Tf) o (Cb,Tb) = (Cf + Tf*Cb, Tf*Tb)."""
-    acc = parts[-1].astype(np.float32).copy()
-    for k in range(parts.shape[0] - 2, -1, -1):
-        b = parts[k]
-        acc[..., :3] = np.float32(acc[..., 3:4] * b[..., :3] + acc[..., :3])
-        acc[..., 3] = acc[..., 3] * b[..., 3]
-    return acc[..., :3]
+    """parts [G, ..., 4] ordered back->front -> [..., 3]: (Cf,Tf) o (Cb,Tb) = (fma(Tf, Cb, Cf), Tf*Tb),
+    the colour update in one rounding as mpiv_combine_ct computes it (oracle_combine_ct)."""
+    parts = np.ascontiguousarray(parts, np.float32)
+    out = np.empty(parts.shape[1:-1] + (3,), np.float32)
+    lib().oracle_combine_ct(_fp(parts), parts.shape[0], int(np.prod(parts.shape[1:-1])), _fp(out))
+    return out
 
 
 def synth_mpi(seed: int, H: int, W: int, p0: int, p1: int) -> np.ndarray:
