@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MPIV_ABI_VERSION 15
+#define MPIV_ABI_VERSION 16
 
 enum {
     MPIV_OK = 0,
@@ -67,6 +67,7 @@ int mpiv_debug_set(const char *name, int value);
  *   "plane_sweep"                        {B, Hs, Ws, C, D, Ht, Wt} (mpiv_plane_sweep)
  *   "render_packed_ct_rows"              {H, W, P, V, y_begin, y_end} (mpiv_render_packed_ct_rows)
  *   "render_packed_u8"                   {H, W, P, V}        (mpiv_render_packed_u8)
+ *   "render_packed_f16", "render_packed_f16_ct"  {H, W, P, V} (mpiv_render_packed_f16[_ct])
  *   "render_net_output"                  {B, H, W, P}        (mpiv_render_net_output)
  * Fails while a debug option is set (it reports production routes only). */
 int mpiv_route(const char *entry, const int64_t *args, int nargs, char *name, int name_cap, int64_t *grid_threads);
@@ -419,6 +420,32 @@ int mpiv_unpack_planes_u8(const uint32_t *packed, int H, int W, int P, float *ou
 /* Counter-based synthetic u8 MPI (mpiv_synth_mpi_packed's hash, one byte per channel =
  * the top 8 bits of its hash, plane 0 alpha 255) into the packed u8 layout. */
 int mpiv_synth_mpi_packed_u8(uint32_t seed, int H, int W, int p_begin, int p_end, uint32_t *packed, void *stream);
+
+/* ---- half-precision RGBA MPIs (a network's output under autocast, RGBA16F / EXR assets).
+ * Rendering an f16 MPI is defined as rendering mpi.float(): half -> float is exact. -------- */
+
+/* One view [H,W,P,4] half (IEEE binary16 bits; element strides strides[4] = H,W,P,C) -> packed
+ * f16 planes [P][H+4][W+4][4] half (8-B texels in RGBA order; 8-B aligned) with a 2-texel zero
+ * border: mpiv_pack_planes' layout at 8 B per texel. */
+int mpiv_pack_planes_f16(const uint16_t *mpi_view, const int64_t strides[4], int H, int W, int P,
+                         uint16_t *packed, void *stream);
+
+/* Packed f16 planes -> packed float planes out [P][H+4][W+4] float4 (mpiv_pack_planes' layout,
+ * 16-B aligned), every channel converted exactly (subnormals, signed zeros, infinities; NaN
+ * stays NaN); the border stays +0.  A caller that renders one f16 MPI again and again at 8 or more
+ * views per launch converts it once with this (0.52 ms at 1024x1024x128) and runs the float kernel,
+ * which is faster there (bit-identical frames); for a single launch that pays from about 64 views. */
+int mpiv_unpack_planes_f16(const uint16_t *packed, int H, int W, int P, float *out, void *stream);
+
+/* mpiv_render_packed on a packed f16 MPI: out [V,H,W,3] fp32 equals mpiv_render_packed on the
+ * float MPI of mpiv_unpack_planes_f16 bit for bit (each tap is converted exactly before the
+ * reference's blend).  H, W >= 2. */
+int mpiv_render_packed_f16(const uint16_t *packed, int H, int W, int P, const float *homs, int V,
+                           float *out, void *stream);
+
+/* mpiv_render_packed_ct on a packed f16 MPI (plane-range partial (C, T) [V,H,W,4], 16-B aligned). */
+int mpiv_render_packed_f16_ct(const uint16_t *packed, int H, int W, int P, int p_begin, int p_end,
+                              int back, const float *homs, int V, float *ct, void *stream);
 
 /* ---- diagnostics ------------------------------------------------------------ */
 

@@ -87,11 +87,15 @@ _SIGS = {
     "mpiv_assemble_mpi_backward": [_vp, _c_i64p, _vp, _c_i64p, _vp, _c_i64p, _int, _int, _int, _int, _vp, _vp,
                                    _vp],
     "mpiv_tile_order": [_int, _int, _int, ctypes.POINTER(ctypes.c_int32)],
+    "mpiv_pack_planes_f16": [_vp, _c_i64p, _int, _int, _int, _vp, _vp],
+    "mpiv_unpack_planes_f16": [_vp, _int, _int, _int, _vp, _vp],
+    "mpiv_render_packed_f16": [_vp, _int, _int, _int, _vp, _int, _vp, _vp],
+    "mpiv_render_packed_f16_ct": [_vp, _int, _int, _int, _int, _int, _int, _vp, _int, _vp, _vp],
 }
 EXPORTS = tuple(_SIGS) + ("mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
                           "mpiv_render_backward_abort_flag",
                           "mpiv_render_backward_workspace_size_min", "mpiv_build_id", "mpiv_debug_set")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _lib = None
 _lib_ab = None
@@ -457,7 +461,7 @@ def unpack_planes_u8(packed: torch.Tensor) -> torch.Tensor:
 # float rows kernel at 125 views: 26.6 ms vs 29.8 for the u8 kernel, VALU-bound on the exact
 # per-tap conversion; at one view the u8 kernel reads 4x fewer bytes and wins, 0.31 vs 0.38 ms).
 U8_FLOAT_MIN_VIEWS = int(os.environ.get("MPIV_U8_FLOAT_MIN_VIEWS", "32"))
-_U8_FLOAT: dict = {}
+_U8_FLOAT: dict = {}  # device -> (key, weak reference to the u8 / f16 MPI, its float copy)
 
 
 def _wrote(t: torch.Tensor) -> None:
@@ -466,12 +470,13 @@ def _wrote(t: torch.Tensor) -> None:
     torch.autograd.graph.increment_version(t)
 
 
-def u8_float_copy(packed: torch.Tensor) -> torch.Tensor:
-    """The packed float copy of a packed u8 MPI, memoised per device on the tensor object, its
-    storage, version counter and the current stream (a camera path converts its MPI once; an
-    in-place edit, a refill through pack_planes_u8(out=) or a new MPI converts again; a copy is
-    only read on the stream that made it).  One entry per device: the copy is 4x the u8 MPI
-    (2.2 GB at config 4); it is dropped when the u8 MPI is freed, or by clear_u8_float_copies()."""
+def packed_float_copy(packed: torch.Tensor) -> torch.Tensor:
+    """The packed float copy of a packed u8 or f16 MPI (by its dtype: int32 words / float16 texels),
+    memoised per device on the tensor object, its storage, version counter and the current stream
+    (a camera path converts its MPI once; an in-place edit, a refill through pack_planes_u8(out=) /
+    pack_planes_f16(out=) or a new MPI converts again; a copy is only read on the stream that made
+    it).  One entry per device, whatever the format: the copy is 4x the u8 MPI, 2x the f16 one
+    (2.2 GB at config 4); it is dropped when its MPI is freed, or by clear_float_copies()."""
     dev = packed.device
     key = (id(packed), packed.data_ptr(), packed._version, tuple(packed.shape),
            torch.cuda.current_stream(dev).cuda_stream)
@@ -479,10 +484,22 @@ def u8_float_copy(packed: torch.Tensor) -> torch.Tensor:
     if ent is not None and ent[0] == key and ent[1]() is packed:
         return ent[2]
     _U8_FLOAT.pop(dev, None)  # free the old copy first
-    f = unpack_planes_u8(packed)
+    f = unpack_planes_f16(packed) if packed.dtype == torch.float16 else unpack_planes_u8(packed)
     _U8_FLOAT[dev] = (key, weakref.ref(packed), f)
     weakref.finalize(packed, _drop_u8_float, dev, key)
     return f
+
+
+def u8_float_copy(packed: torch.Tensor) -> torch.Tensor:
+    """packed_float_copy of a packed u8 MPI."""
+    _u8_hw(packed)
+    return packed_float_copy(packed)
+
+
+def f16_float_copy(packed: torch.Tensor) -> torch.Tensor:
+    """packed_float_copy of a packed f16 MPI."""
+    _f16_hw(packed)
+    return packed_float_copy(packed)
 
 
 def _drop_u8_float(dev, key) -> None:
@@ -491,12 +508,15 @@ def _drop_u8_float(dev, key) -> None:
         del _U8_FLOAT[dev]
 
 
-def clear_u8_float_copies(device=None) -> None:
-    """Free the memoised float copies of u8 MPIs (all devices, or `device`'s)."""
+def clear_float_copies(device=None) -> None:
+    """Free the memoised float copies of u8 and f16 MPIs (all devices, or `device`'s)."""
     if device is None:
         _U8_FLOAT.clear()
     else:
         _U8_FLOAT.pop(torch.device(device), None)
+
+
+clear_u8_float_copies = clear_float_copies
 
 
 def render_packed_u8(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None = None,
@@ -536,6 +556,104 @@ def render_packed_u8_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_
     else:
         _check_out(out, (V, H, W, 4), dev, "render_packed_u8_ct")
     _call("mpiv_render_packed_u8_ct", packed, H, W, P, p_begin, p_end, int(back), h, V, out, _stream(dev))
+    return out
+
+
+def pack_planes_f16(view: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One half-precision MPI view [H, W, P, 4] float16 (any strides) -> packed f16 planes
+    [P, H+4, W+4, 4] float16 (8-B texels) with the zero border."""
+    if not isinstance(view, torch.Tensor):
+        raise TypeError(f"expected a torch.Tensor, got {type(view).__name__}")
+    if view.dtype != torch.float16:
+        raise RuntimeError(f"pack_planes_f16 expects a float16 [H, W, P, 4] tensor, got {view.dtype}")
+    if view.device.type != "cuda":
+        raise RuntimeError("mpi_vision_amd kernels need ROCm device tensors; there is no CPU path")
+    dev = view.device
+    H, W, P, C = view.shape
+    if C != 4:
+        raise RuntimeError(f"MPI texels must have 4 channels (RGBA), got {C}")
+    shape = packed_shape(H, W, P)
+    if out is None:
+        packed = torch.empty(shape, device=dev, dtype=torch.float16)
+    elif tuple(out.shape) != shape or out.dtype != torch.float16 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"pack_planes_f16: out must be a contiguous float16 {shape} tensor on {dev}")
+    else:
+        packed = out
+    _call("mpiv_pack_planes_f16", view, _strides(view), H, W, P, packed, _stream(dev))
+    if out is not None:
+        _wrote(packed)
+    return packed
+
+
+def _f16_hw(packed: torch.Tensor):
+    if not isinstance(packed, torch.Tensor):
+        raise TypeError(f"expected a torch.Tensor, got {type(packed).__name__}")
+    if packed.dtype != torch.float16 or packed.dim() != 4 or packed.shape[-1] != 4 or not packed.is_contiguous():
+        raise RuntimeError(f"packed f16 MPI must be a contiguous float16 [P, H+4, W+4, 4] tensor, got {packed.dtype} "
+                           f"{tuple(packed.shape)}")
+    if packed.device.type != "cuda":
+        raise RuntimeError("mpi_vision_amd kernels need ROCm device tensors; there is no CPU path")
+    return packed.shape[0], packed.shape[1] - 2 * PAD, packed.shape[2] - 2 * PAD
+
+
+def unpack_planes_f16(packed: torch.Tensor) -> torch.Tensor:
+    """packed f16 [P,H+4,W+4,4] -> the packed float MPI [P,H+4,W+4,4] of mpi.float() (exact)."""
+    P, H, W = _f16_hw(packed)
+    out = torch.empty(packed_shape(H, W, P), device=packed.device, dtype=torch.float32)
+    _call("mpiv_unpack_planes_f16", packed, H, W, P, out, _stream(packed.device))
+    return out
+
+
+# Views per launch from which render_packed_f16 renders a half MPI through its float copy: on config 4
+# the f16 kernel wins up to 4 views (one view 0.265 vs 0.376 ms for the float kernel), the float rows
+# kernel from 8 (1.49 vs 1.56 ms; 125 views 20.2 vs 23.4), on config 2 from 8 too (0.147 vs 0.190)
+# (profiles/f16_render.jsonl, DESIGN.md §4 "f16 texels").  These are steady-state kernel times: the
+# threshold is for a packed MPI that is rendered again and again (the copy, 0.52 ms at config 4, is
+# memoised).  A caller that packs, renders ONE launch and drops the MPI (mpi_render_view_f16) pays the
+# copy every time: copy + float kernel beat the f16 kernel only from F16_FLOAT_ONCE_MIN_VIEWS views
+# (config 4 at 32 views 5.50 + 0.52 vs 6.00 ms, a tie; at 64 views 10.46 + 0.52 vs 11.96).
+F16_FLOAT_MIN_VIEWS = int(os.environ.get("MPIV_F16_FLOAT_MIN_VIEWS", "8"))
+F16_FLOAT_ONCE_MIN_VIEWS = 64
+
+
+def render_packed_f16(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None = None,
+                      route_float: bool | None = None) -> torch.Tensor:
+    """packed f16 [P,H+4,W+4,4] + homs [V,P,9] -> [V,H,W,3] fp32, bit-identical to rendering the
+    float MPI mpi.float() (render_f16.hip: half the texel bytes of the float render).  Launches of
+    >= F16_FLOAT_MIN_VIEWS views (route_float None) render the MPI's exact float copy
+    (f16_float_copy, converted once per MPI) with the float kernel instead: the same bits, faster
+    where the texture path binds (it costs the float copy's memory, 2x the f16 MPI)."""
+    P, H, W = _f16_hw(packed)
+    if route_float is None:
+        route_float = homs.shape[0] >= F16_FLOAT_MIN_VIEWS
+    if route_float:
+        return render_packed(f16_float_copy(packed), homs, out=out)
+    dev = packed.device
+    V = homs.shape[0]
+    h = _up(homs.reshape(V, P, 9), dev)
+    if out is None:
+        out = torch.empty((V, H, W, 3), device=dev, dtype=torch.float32)
+    else:
+        _check_out(out, (V, H, W, 3), dev, "render_packed_f16")
+    if V == 0:
+        return out
+    _call("mpiv_render_packed_f16", packed, H, W, P, h, V, out, _stream(dev))
+    return out
+
+
+def render_packed_f16_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_begin: int = 0,
+                         p_end: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Plane-range partial (C, T) [V,H,W,4] of a packed f16 MPI (plane sharding)."""
+    P, H, W = _f16_hw(packed)
+    dev = packed.device
+    p_end = P if p_end is None else p_end
+    V = homs.shape[0]
+    h = _up(homs.reshape(V, P, 9), dev)
+    if out is None:
+        out = torch.empty((V, H, W, 4), device=dev, dtype=torch.float32)
+    else:
+        _check_out(out, (V, H, W, 4), dev, "render_packed_f16_ct")
+    _call("mpiv_render_packed_f16_ct", packed, H, W, P, p_begin, p_end, int(back), h, V, out, _stream(dev))
     return out
 
 

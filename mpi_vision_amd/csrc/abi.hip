@@ -27,6 +27,7 @@
 #include "assemble.hip"
 #include "synth.hip"
 #include "render_u8.hip"
+#include "render_f16.hip"
 
 namespace {
 
@@ -2071,6 +2072,94 @@ int mpiv_render_packed_u8_ct(const uint32_t* packed, int H, int W, int P, int p_
     return render_u8_impl(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
 }
 
+// ---- half-precision RGBA MPI (render_f16.hip) ----------------------------------------
+
+int mpiv_pack_planes_f16(const uint16_t* mpi, const int64_t st[4], int H, int W, int P, uint16_t* packed,
+                         void* stream) {
+    const char* nm = "mpiv_pack_planes_f16";
+    if (!mpi || !st || !packed) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if (reinterpret_cast<uintptr_t>(packed) & 7) return fail(MPIV_ERR_ARG, "%s: alignment (packed 8 B)", nm);
+    const int64_t npix = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
+    if (npix * 8 >= (int64_t)kOOB || blocks(P, kPackPl) > kMaxGridYZ)
+        return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or too many planes", nm);
+    const NativeStrides s{0, st[0], st[1], st[2], st[3]};
+    pack_planes_f16_kernel<<<dim3(blocks(npix, kPackPix), blocks(P, kPackPl)), 256, 0, S(stream)>>>(
+        mpi, s, H, W, P, make_fastdiv((unsigned)(W + 2 * kPad)), reinterpret_cast<uint2*>(packed), npix);
+    return launched(nm);
+}
+
+int mpiv_unpack_planes_f16(const uint16_t* packed, int H, int W, int P, float* out, void* stream) {
+    const char* nm = "mpiv_unpack_planes_f16";
+    if (!packed || !out) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if ((reinterpret_cast<uintptr_t>(packed) & 7) || !aligned16(out))
+        return fail(MPIV_ERR_ARG, "%s: alignment (packed 8 B, out 16 B)", nm);
+    const int64_t n = (int64_t)P * (H + 2 * kPad) * (W + 2 * kPad);
+    const int64_t nb = std::min<int64_t>(blocks(n, 256), 1 << 20);
+    unpack_planes_f16_kernel<<<(unsigned)nb, 256, 0, S(stream)>>>(reinterpret_cast<const uint2*>(packed),
+                                                                 reinterpret_cast<float4*>(out), n);
+    return launched(nm);
+}
+
+static int render_f16_impl(const uint16_t* packed, int H, int W, int P, int p_begin, int p_end, int back,
+                           const float* homs, int V, float* out, bool ct, void* stream) {
+    const char* nm = ct ? "mpiv_render_packed_f16_ct" : "mpiv_render_packed_f16";
+    if (!packed || !homs || !out) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (V <= 0 || H < 2 || W < 2 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape (H, W >= 2)", nm);
+    if (p_begin < 0 || p_end > P || p_begin >= p_end) return fail(MPIV_ERR_ARG, "%s: bad plane range", nm);
+    if ((reinterpret_cast<uintptr_t>(packed) & 7) || (ct && !aligned16(out)))
+        return fail(MPIV_ERR_ARG, "%s: alignment (packed 8 B, ct 16 B)", nm);
+    const int64_t npix = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
+    if (npix * 8 >= (int64_t)kOOB || H >= (1 << 22) || W >= (1 << 22))
+        return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or a side >= 2^22", nm);
+    const RenderGeom g = make_geom(H, W, P);
+    F16Geom fg;
+    fg.row = g.Wp * 8;
+    fg.org = (kPad * g.Wp + kPad) * 8;
+    fg.plane_bytes = (int)(npix * 8);
+    // The u8 render's dispatch (render_u8_impl): 4 rows per work-item with vertical tap reuse where the
+    // MPI is square or the launch fills the chip (>= 2048 tiles of 64x32), else 2 plain rows; with
+    // reuse, 4 rows in flight when the launch leaves the SIMDs few waves (under 2048 blocks), else 2.
+    const float sxr = (float)W / (float)(H - 1), syr = (float)H / (float)(W - 1);
+    const bool square = sxr >= 0.8f && sxr <= 1.25f && syr >= 0.8f && syr <= 1.25f;
+    const bool big = (int64_t)blocks(W, kTileX) * blocks(H, 4 * 8) * V >= 2048;
+    const bool vs = square || big;
+    const int R = vs ? 4 : 2;
+    const int64_t nb = (int64_t)blocks(W, kTileX) * blocks(H, 4 * R) * V;
+    if (nb > kMaxGridX) return fail(MPIV_ERR_ARG, "%s: too many blocks", nm);
+    const int d = vs && nb < 2048 ? 4 : 2;
+    if (g_route)  // every template argument, as rocprof's demangled name shows it
+        return note_route(nb, 256, "render_f16_kernel<%s, %d, %s, %d>", ct ? "true" : "false", R, vs ? "true" : "false", d);
+    const uint2* pk = reinterpret_cast<const uint2*>(packed);
+    hipStream_t q = S(stream);
+    const int csp = opt(kOptRenderColsep);  // the column-separable issue path (render.hip ColSet)
+    const int ord = render_tile_order(V);
+#define MPIV_F16(CT, RR, VV, DD)                                                                                   \
+    render_f16_kernel<CT, RR, VV, DD><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, fg, V, p_begin, p_end, CT ? back : 1, \
+                                                                   homs, out, csp, ord)
+    if (vs && d == 4) {
+        if (ct) MPIV_F16(true, 4, true, 4);
+        else MPIV_F16(false, 4, true, 4);
+    } else if (vs) {
+        if (ct) MPIV_F16(true, 4, true, 2);
+        else MPIV_F16(false, 4, true, 2);
+    } else if (ct) MPIV_F16(true, 2, false, 2);
+    else MPIV_F16(false, 2, false, 2);
+#undef MPIV_F16
+    return launched(nm);
+}
+
+int mpiv_render_packed_f16(const uint16_t* packed, int H, int W, int P, const float* homs, int V, float* out,
+                           void* stream) {
+    return render_f16_impl(packed, H, W, P, 0, P, 1, homs, V, out, false, stream);
+}
+
+int mpiv_render_packed_f16_ct(const uint16_t* packed, int H, int W, int P, int p_begin, int p_end, int back,
+                              const float* homs, int V, float* ct, void* stream) {
+    return render_f16_impl(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
+}
+
 int mpiv_tile_order(int ntiles, int tiles_x, int order, int32_t* out) {
     if (!out) return fail(MPIV_ERR_ARG, "mpiv_tile_order: null pointer");
     if (ntiles <= 0 || tiles_x <= 0 || ntiles % tiles_x)
@@ -2124,6 +2213,9 @@ int mpiv_route(const char* entry, const int64_t* a, int na, char* name, int name
     } else if (strcmp(entry, "render_packed_u8") == 0 && na == 4) {
         rc = render_u8_impl(reinterpret_cast<const uint32_t*>(d), (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d,
                             (int)a[3], d, false, nullptr);
+    } else if ((strcmp(entry, "render_packed_f16") == 0 || strcmp(entry, "render_packed_f16_ct") == 0) && na == 4) {
+        rc = render_f16_impl(reinterpret_cast<const uint16_t*>(d), (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d,
+                             (int)a[3], d, strcmp(entry, "render_packed_f16_ct") == 0, nullptr);
     } else if (strcmp(entry, "render_net_output") == 0 && na == 4) {
         const int64_t B = a[0], H = a[1], W = a[2], P = a[3];
         const int64_t ps[4] = {(2 * P + 3) * H * W, H * W, W, 1}, fs[4] = {H * W * 3, W * 3, 3, 1};

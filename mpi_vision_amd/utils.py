@@ -187,6 +187,42 @@ def mpi_render_view_u8(rgba_layers_u8, tgt_pose, planes, intrinsics):
     return out
 
 
+def mpi_render_view_f16(rgba_layers_f16, tgt_pose, planes, intrinsics):
+    """mpi_render_view_torch for a half-precision MPI [B, H, W, P, 4] float16 (a network's output
+    under autocast, an RGBA16F / EXR asset): returns exactly
+    mpi_render_view_torch(rgba_layers_f16.float(), tgt_pose, planes, intrinsics)
+    in fp32 without the float copy: each view is packed at 8 B per texel and rendered by
+    render_f16.hip, which converts every tap to float (exactly) before the reference's blend.
+    The packed MPI is a temporary of this call, so a float copy would serve one launch only: a
+    stride-0 batch takes the float-copy route of _lib.render_packed_f16 only from
+    _lib.F16_FLOAT_ONCE_MIN_VIEWS views, where copy + float kernel beat the f16 kernel; below, and
+    for a non-broadcast batch, the f16 kernel renders (a caller that renders one MPI many times
+    packs it once and calls _lib.render_packed_f16, which routes a reused MPI from fewer views).
+    Inference only (no autograd through half texels).  An extension of the drop-in API."""
+    if not isinstance(rgba_layers_f16, torch.Tensor) or rgba_layers_f16.dtype != torch.float16:
+        raise RuntimeError("mpi_render_view_f16 expects a float16 [B, H, W, P, 4] tensor")
+    batch_size = tgt_pose.shape[0]
+    n_planes = len(planes)
+    depths = planes.reshape([n_planes, 1])
+    if tgt_pose.is_cuda:
+        homs = _host.render_homographies_device(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
+    else:
+        homs = _host.render_homographies(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
+    B, H, W, P, _ = rgba_layers_f16.shape
+    if B != batch_size or P != n_planes:
+        raise RuntimeError(f"shape mismatch: MPI batch/planes {B}/{P} vs poses/planes {batch_size}/{n_planes}")
+    homs = homs.reshape(B, P, 9)
+    if B > 1 and rgba_layers_f16.stride(0) == 0:  # one MPI, many views: pack once
+        return _lib.render_packed_f16(_lib.pack_planes_f16(rgba_layers_f16[0]), homs,
+                                      route_float=B >= _lib.F16_FLOAT_ONCE_MIN_VIEWS)
+    out = torch.empty((B, H, W, 3), device=rgba_layers_f16.device, dtype=torch.float32)
+    packed = None
+    for b in range(B):
+        packed = _lib.pack_planes_f16(rgba_layers_f16[b], out=packed)
+        _lib.render_packed_f16(packed, homs[b:b + 1], out=out[b:b + 1], route_float=False)
+    return out
+
+
 def mpi_from_net_output(mpi_pred, dep):
     """The notebook's MPI assembly (fast-torch-stereo-vision.ipynb cell 10 L79-111):
     the network output [B, 2P+3, H, W] (P blend weights, P alphas, background rgb) and

@@ -63,6 +63,51 @@ int main() {
     EXPECT(mpiv_probe_gather(f, 16384, 0, 1, f, nullptr) == MPIV_ERR_ARG);
     EXPECT(mpiv_probe_gather(f, 4096, 1, 1, f, nullptr) == MPIV_ERR_ARG);
     EXPECT(mpiv_selftest_div_const(0, nullptr, nullptr) == MPIV_ERR_ARG);
+    // half-precision MPI entries: null pointers, shapes, plane range, alignment (packed 8 B, ct / out 16 B)
+    {
+        uint16_t* h = static_cast<uint16_t*>(p);
+        uint16_t* h4 = reinterpret_cast<uint16_t*>(4);
+        float* f8 = reinterpret_cast<float*>(8);
+        EXPECT(mpiv_pack_planes_f16(nullptr, st4, 4, 4, 2, h, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_pack_planes_f16(h, nullptr, 4, 4, 2, h, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_pack_planes_f16(h, st4, 4, 4, 2, nullptr, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "null pointer") != nullptr);
+        EXPECT(mpiv_pack_planes_f16(h, st4, 4, 0, 2, h, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "bad shape") != nullptr);
+        EXPECT(mpiv_pack_planes_f16(h, st4, 4, 4, 2, h4, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "alignment") != nullptr);
+        EXPECT(mpiv_pack_planes_f16(h, st4, 20000, 20000, 2, h, nullptr) == MPIV_ERR_ARG);  // plane >= 2 GiB
+        EXPECT(mpiv_unpack_planes_f16(nullptr, 4, 4, 2, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_unpack_planes_f16(h, 4, 4, 2, nullptr, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_unpack_planes_f16(h, 4, 4, 0, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "bad shape") != nullptr);
+        EXPECT(mpiv_unpack_planes_f16(h4, 4, 4, 2, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_unpack_planes_f16(h, 4, 4, 2, f8, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "alignment") != nullptr);
+        EXPECT(mpiv_render_packed_f16(nullptr, 4, 4, 2, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_f16(h, 4, 4, 2, nullptr, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_f16(h, 4, 4, 2, f, 1, nullptr, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "null pointer") != nullptr);
+        EXPECT(mpiv_render_packed_f16(h, 1, 4, 2, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_f16(h, 4, 4, 2, f, 0, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "bad shape") != nullptr);
+        EXPECT(mpiv_render_packed_f16(h4, 4, 4, 2, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "alignment") != nullptr);
+        EXPECT(mpiv_render_packed_f16(h, 20000, 20000, 2, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_f16_ct(h, 4, 4, 8, 0, 8, 1, f, 1, nullptr, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_f16_ct(h, 4, 4, 8, 5, 3, 0, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "plane range") != nullptr);
+        EXPECT(mpiv_render_packed_f16_ct(h, 4, 4, 8, 0, 9, 0, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_f16_ct(h, 4, 4, 8, 0, 8, 1, f, 1, f8, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "alignment") != nullptr);
+        char name[160];
+        int64_t grid = 0;
+        const int64_t a4[4] = {1024, 1024, 128, 1};
+        EXPECT(mpiv_route("render_packed_f16", a4, 4, name, sizeof(name), &grid) == MPIV_OK);
+        EXPECT(std::strncmp(name, "render_f16_kernel<", 18) == 0 && grid == 16 * 64 * 256);
+        EXPECT(mpiv_route("render_packed_f16_ct", a4, 4, name, sizeof(name), &grid) == MPIV_OK);
+        EXPECT(std::strncmp(name, "render_f16_kernel<true", 22) == 0);
+    }
     // the tile order on an exact-size heap buffer: a permutation; bad arguments rejected
     {
         std::vector<int32_t> ord(9 * 5);
