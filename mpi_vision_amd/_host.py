@@ -112,7 +112,7 @@ def _f32_on(t: torch.Tensor, dev) -> torch.Tensor:
     return t if (t.dtype == _F32 and t.device == dev) else t.to(device=dev, dtype=_F32)
 
 
-def _kinv_device(intrinsics: torch.Tensor, batch: int, dev, sid=None, psv: bool = False) -> torch.Tensor:
+def _kinv_device(intrinsics: torch.Tensor, batch: int, dev, sid=None, psv: bool = False, with_k: bool = False):
     """inverse(K) [batch,3,3] on `dev` for a device-resident intrinsics tensor, memoised on
     that tensor OBJECT and its version counter (an in-place update bumps it; a new tensor
     is a new object), so a camera path that reuses one intrinsics tensor reads it back to
@@ -121,7 +121,12 @@ def _kinv_device(intrinsics: torch.Tensor, batch: int, dev, sid=None, psv: bool 
 
     psv=False (render): the reference inverts its materialised [P,B,3,3] repeat of K
     (utils.py:225-228 -> :60), so K is inverted contiguous.  psv=True: the caller's own layout
-    (psv_inverse, utils.py:370)."""
+    (psv_inverse, utils.py:370).
+
+    with_k (render only): returns (inverse, K), where K is None outside a HIP-graph capture (the
+    caller reads its own tensor) and, under capture, the [batch,3,3] intrinsics the memoised
+    inverse belongs to, as a constant of the graph like the inverse itself -- so a replay never
+    pairs an updated K with the captured inverse."""
     try:
         ver = intrinsics._version
     except RuntimeError:  # inference tensors track no version: no memo
@@ -132,27 +137,45 @@ def _kinv_device(intrinsics: torch.Tensor, batch: int, dev, sid=None, psv: bool 
     ent = _KINV_DEV.get((id(intrinsics), psv))
     same = (ver is not None and ent is not None and ent[0]() is intrinsics and ent[1] == ver and ent[2] == batch
             and ent[3].device == dev)
-    if same and ent[4] == stream:
-        return ent[3]
     if torch.cuda.is_current_stream_capturing():
         # HIP-graph capture (torch.cuda.graph / make_graphed_callables): a device-to-host copy cannot be
-        # captured.  The inverse memoised during the warm-up (on another stream) is copied device to
-        # device instead -- a captured copy into the graph's own memory pool, so replays never read
-        # memory the memo may free.
+        # captured, and the memo's device tensor must not be: a later eager call on another stream, a
+        # version bump or the eviction frees it, and a replay would read freed memory.  The inverse
+        # memoised during the warm-up (on any stream) is written from its HOST values into a fresh
+        # tensor of the graph's own pool (captured_constant): a constant of the captured graph.
         if same:
-            return ent[3].clone()
+            kinv = captured_constant(ent[5], dev)
+            return (kinv, captured_constant(ent[6], dev)) if with_k else kinv
         raise RuntimeError("mpi_vision_amd: inverse(intrinsics) is not memoised for this tensor; run the call "
                            "once outside the HIP-graph capture (the warm-up) first")
+    if same and ent[4] == stream:
+        return (ent[3], None) if with_k else ent[3]
     if psv:
-        kinv = psv_inverse(intrinsics, batch).to(dev)
+        K = None
+        host = psv_inverse(intrinsics, batch)
     else:
         K = _cpu32(intrinsics).expand(batch, 3, 3).contiguous()
-        kinv = _inverse_cached(K).to(dev)
+        host = _inverse_cached(K)
+    kinv = host.to(dev)
     if ver is not None:
         if len(_KINV_DEV) >= 64:
             _KINV_DEV.clear()
-        _KINV_DEV[(id(intrinsics), psv)] = (weakref.ref(intrinsics), ver, batch, kinv, stream)
-    return kinv
+        _KINV_DEV[(id(intrinsics), psv)] = (weakref.ref(intrinsics), ver, batch, kinv, stream, host, K)
+    return (kinv, None) if with_k else kinv
+
+
+def captured_constant(host: torch.Tensor, dev) -> torch.Tensor:
+    """A fresh fp32 tensor on `dev` holding the values of the small fp32 CPU tensor `host`, written
+    by kernels whose ARGUMENTS carry the values (ones, then one multiply per element by its value:
+    1 * x is x bit for bit, signed zeros, infinities and NaN included).  Under a HIP-graph capture the
+    tensor comes from the graph's memory pool and every replay writes it again from the captured
+    kernel arguments: no copy from host memory or from a memoised device tensor is recorded, so
+    nothing a replay reads can be freed or replaced behind the graph."""
+    vals = host.reshape(-1).tolist()
+    out = torch.ones(len(vals), dtype=_F32, device=dev)
+    if vals:
+        torch._foreach_mul_(list(out.unbind(0)), vals)
+    return out.reshape(host.shape)
 
 
 def render_homographies_device(pose: torch.Tensor, depths: torch.Tensor, intrinsics: torch.Tensor,
@@ -169,7 +192,9 @@ def render_homographies_device(pose: torch.Tensor, depths: torch.Tensor, intrins
     if tuple(K.shape) != (batch, 3, 3):
         K = K.expand(batch, 3, 3)
     K = K.contiguous()
-    kinv = _kinv_device(intrinsics, batch, dev)
+    kinv, k_const = _kinv_device(intrinsics, batch, dev, with_k=True)
+    if k_const is not None:  # under a HIP-graph capture: the K its inverse was taken from
+        K = k_const
     P = d.shape[0]
     H = torch.empty((batch, P, 9), dtype=_F32, device=dev)
     _lib._call("mpiv_render_homographies_device", pose_d, d, K, kinv, batch, P, H, _lib._stream(dev))

@@ -342,12 +342,26 @@ def _stream(dev):
     return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def _up(x: torch.Tensor, dev) -> torch.Tensor:
+def host_under_capture(what: str) -> None:
+    """Raise if the current stream is capturing a HIP graph: `what` names a per-call matrix argument
+    that lives on the host.  Its upload would be recorded as a copy from a temporary host buffer
+    (page-locked: gone by the first replay; pageable: not capturable at all), and every replay would
+    read whatever is there then."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"mpi_vision_amd: {what} is a host (CPU) tensor; under a HIP-graph capture every per-call "
+                           "matrix must be a device tensor (a static input of the graph), because a captured "
+                           "upload would read a temporary host buffer on every replay")
+
+
+def _up(x: torch.Tensor, dev, what: str = "a matrix argument") -> torch.Tensor:
     """Upload a small host-computed matrix buffer (contiguous fp32).  A page-locked host
     buffer is copied asynchronously on the current stream (torch's pinned allocator keeps
-    it alive until that copy has run)."""
-    if x.device.type == "cpu" and x.is_pinned() and x.dtype == torch.float32 and x.is_contiguous():
-        return x.to(device=dev, non_blocking=True)
+    it alive until that copy has run).  Under a HIP-graph capture a host buffer raises
+    (host_under_capture), before anything is launched."""
+    if x.device.type == "cpu":
+        host_under_capture(what)
+        if x.is_pinned() and x.dtype == torch.float32 and x.is_contiguous():
+            return x.to(device=dev, non_blocking=True)
     return x.to(device=dev, dtype=torch.float32).contiguous()
 
 
@@ -476,8 +490,14 @@ def packed_float_copy(packed: torch.Tensor) -> torch.Tensor:
     (a camera path converts its MPI once; an in-place edit, a refill through pack_planes_u8(out=) /
     pack_planes_f16(out=) or a new MPI converts again; a copy is only read on the stream that made
     it).  One entry per device, whatever the format: the copy is 4x the u8 MPI, 2x the f16 one
-    (2.2 GB at config 4); it is dropped when its MPI is freed, or by clear_float_copies()."""
+    (2.2 GB at config 4); it is dropped when its MPI is freed, or by clear_float_copies().  Under a
+    HIP-graph capture the memo is neither read nor written: the conversion is captured."""
     dev = packed.device
+    if torch.cuda.is_current_stream_capturing():
+        # HIP-graph capture: the conversion is part of the graph, into a fresh tensor of the graph's own
+        # pool -- the packed MPI is a static input whose contents change between replays, so a memo hit
+        # must not skip it, and the memo's copy (freed by the next MPI) must not be captured
+        return unpack_planes_f16(packed) if packed.dtype == torch.float16 else unpack_planes_u8(packed)
     key = (id(packed), packed.data_ptr(), packed._version, tuple(packed.shape),
            torch.cuda.current_stream(dev).cuda_stream)
     ent = _U8_FLOAT.get(dev)
@@ -529,10 +549,12 @@ def render_packed_u8(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor
     if route_float is None:
         route_float = homs.shape[0] >= U8_FLOAT_MIN_VIEWS
     if route_float:
+        if homs.device.type == "cpu":
+            host_under_capture("homs")  # (before the float copy is launched)
         return render_packed(u8_float_copy(packed), homs, out=out)
     dev = packed.device
     V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev)
+    h = _up(homs.reshape(V, P, 9), dev, "homs")
     if out is None:
         out = torch.empty((V, H, W, 3), device=dev, dtype=torch.float32)
     else:
@@ -550,7 +572,7 @@ def render_packed_u8_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_
     dev = packed.device
     p_end = P if p_end is None else p_end
     V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev)
+    h = _up(homs.reshape(V, P, 9), dev, "homs")
     if out is None:
         out = torch.empty((V, H, W, 4), device=dev, dtype=torch.float32)
     else:
@@ -627,10 +649,12 @@ def render_packed_f16(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tenso
     if route_float is None:
         route_float = homs.shape[0] >= F16_FLOAT_MIN_VIEWS
     if route_float:
+        if homs.device.type == "cpu":
+            host_under_capture("homs")  # (before the float copy is launched)
         return render_packed(f16_float_copy(packed), homs, out=out)
     dev = packed.device
     V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev)
+    h = _up(homs.reshape(V, P, 9), dev, "homs")
     if out is None:
         out = torch.empty((V, H, W, 3), device=dev, dtype=torch.float32)
     else:
@@ -648,7 +672,7 @@ def render_packed_f16_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p
     dev = packed.device
     p_end = P if p_end is None else p_end
     V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev)
+    h = _up(homs.reshape(V, P, 9), dev, "homs")
     if out is None:
         out = torch.empty((V, H, W, 4), device=dev, dtype=torch.float32)
     else:
@@ -668,7 +692,7 @@ def render_packed(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | 
     dev = _dev(packed)
     P, H, W = packed_hw(packed)
     V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev)
+    h = _up(homs.reshape(V, P, 9), dev, "homs")
     if out is None:
         out = torch.empty((V, H, W, 3), device=dev, dtype=torch.float32)
     else:
@@ -686,7 +710,7 @@ def render_packed_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_beg
     P, H, W = packed_hw(packed)
     p_end = P if p_end is None else p_end
     V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev)
+    h = _up(homs.reshape(V, P, 9), dev, "homs")
     if out is None:
         out = torch.empty((V, H, W, 4), device=dev, dtype=torch.float32)
     else:
@@ -704,7 +728,7 @@ def render_packed_ct_rows(packed: torch.Tensor, homs: torch.Tensor, back: bool, 
     P, H, W = packed_hw(packed)
     p_end = P if p_end is None else p_end
     V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev)
+    h = _up(homs.reshape(V, P, 9), dev, "homs")
     _check_out(out, (V, H, W, 4), dev, "render_packed_ct_rows")
     _call("mpiv_render_packed_ct_rows", packed, H, W, P, p_begin, p_end, int(back), h, V, y_begin, y_end, out,
           _stream(dev))
@@ -736,7 +760,7 @@ def render(rgba_layers: torch.Tensor, homs: torch.Tensor) -> torch.Tensor:
         raise RuntimeError(f"shape mismatch: MPI batch/planes {B}/{P} vs poses/planes {homs.shape[0]}/{homs.shape[1]}")
     if B > 1 and rgba_layers.stride(0) == 0:
         return render_packed(pack_planes(rgba_layers[0]), homs)
-    h = _up(homs, dev)
+    h = _up(homs, dev, "homs")
     out = torch.empty((B, H, W, 3), device=dev, dtype=torch.float32)
     if RENDER_POLICY == "auto" and chunk_layout_ok(rgba_layers):
         # in place, whole 128-B pixel lines per tap instruction (render_chunk.hip): no pack
@@ -783,7 +807,7 @@ def render_train(rgba_layers: torch.Tensor, homs: torch.Tensor):
     if (B > 1 and rgba_layers.stride(0) == 0) or not chunk_layout_ok(rgba_layers) or \
             4 * 64 * 9 * 16 + P * 36 > _CHUNK_LDS:
         return render(rgba_layers, homs), None
-    h = _up(homs, dev)
+    h = _up(homs, dev, "homs")
     out = torch.empty((B, H, W, 3), device=dev, dtype=torch.float32)
     ckpt = torch.empty((B, (P + 7) // 8, H, W, 4), device=dev, dtype=torch.float32)
     _call("mpiv_render_train", rgba_layers, _strides(rgba_layers), B, H, W, P, h, out, ckpt, _stream(dev))
@@ -884,7 +908,7 @@ def render_backward(rgba_layers: torch.Tensor, homs: torch.Tensor, dout: torch.T
     if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.device != dev:
         raise RuntimeError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on {dev}")
     grad = torch.empty((B, H, W, P, 4), device=dev, dtype=torch.float32)
-    h = _up(homs.reshape(B, P, 9), dev)
+    h = _up(homs.reshape(B, P, 9), dev, "homs")
     dout = dout.contiguous()
     if ckpt is not None and (tuple(ckpt.shape) != (B, (P + 7) // 8, H, W, 4) or not ckpt.is_contiguous()
                              or ckpt.device != dev or ckpt.dtype != torch.float32):
@@ -956,7 +980,7 @@ def assemble_mpi_sampled(mpi_pred: torch.Tensor, fg: torch.Tensor, P: int, homs:
     """assemble_mpi for the backward of a render with homs [B,P,9] only: texel rows no output pixel
     of that render can sample are left unwritten (mpiv_assemble_mpi_sampled)."""
     dev, B, H, W = _net_args(mpi_pred, fg, P)
-    h = _up(homs.reshape(B, P, 9), dev)
+    h = _up(homs.reshape(B, P, 9), dev, "homs")
     out = torch.empty((B, H, W, P, 4), device=dev, dtype=torch.float32)
     _call("mpiv_assemble_mpi_sampled", mpi_pred, _strides(mpi_pred), fg, _strides(fg), B, H, W, P, h, out,
           _stream(dev))
@@ -981,7 +1005,7 @@ def render_net_output(mpi_pred: torch.Tensor, fg: torch.Tensor, P: int, homs: to
     batch element b with homs [B,P,9], in one kernel (render_netout_kernel); bit-identical
     to render(assemble_mpi(...), homs)."""
     dev, B, H, W = _net_args(mpi_pred, fg, P)
-    h = _up(homs.reshape(B, P, 9), dev)
+    h = _up(homs.reshape(B, P, 9), dev, "homs")
     out = torch.empty((B, H, W, 3), device=dev, dtype=torch.float32)
     _call("mpiv_render_net_output", mpi_pred, _strides(mpi_pred), fg, _strides(fg), B, H, W, P, h, out,
           _stream(dev))
@@ -1002,7 +1026,7 @@ def render_net_output_train(mpi_pred: torch.Tensor, fg: torch.Tensor, P: int, ho
     dev, B, H, W = _net_args(mpi_pred, fg, P)
     if not netout_ckpt_ok(H, W, P):
         return render_net_output(mpi_pred, fg, P, homs), None
-    h = _up(homs.reshape(B, P, 9), dev)
+    h = _up(homs.reshape(B, P, 9), dev, "homs")
     out = torch.empty((B, H, W, 3), device=dev, dtype=torch.float32)
     ckpt = torch.empty((B, (P + 7) // 8, H, W, 4), device=dev, dtype=torch.float32)
     _call("mpiv_render_net_output_train", mpi_pred, _strides(mpi_pred), fg, _strides(fg), B, H, W, P, h, out, ckpt,
@@ -1102,6 +1126,17 @@ def _depths_on(depth_planes, dev, sid=None) -> torch.Tensor:
     if sid is None:
         sid = torch.cuda.current_stream(dev).cuda_stream
     key = (tuple(depth_planes), dev.index, sid)
+    if torch.cuda.is_current_stream_capturing():
+        # HIP-graph capture: a host list cannot be uploaded inside the capture (a pageable copy), and the
+        # memo's tensor must not be captured (the eviction frees it under the graph).  After a warm-up
+        # with this list (on any stream) the depths are constants of the graph, written into a fresh
+        # tensor of its own pool from the captured kernel arguments (_host.captured_constant).
+        if not any(k[0] == key[0] and k[1] == key[1] for k in _DEPTHS_DEV):
+            raise RuntimeError("mpi_vision_amd: a Python list of depths under a HIP-graph capture: run the call once "
+                               "outside the capture first (the warm-up), or pass the depths as a device tensor "
+                               "(a static input of the graph)")
+        from ._host import captured_constant
+        return captured_constant(torch.tensor([float(x) for x in key[0]], dtype=torch.float32), dev)
     d = _DEPTHS_DEV.get(key)
     if d is None:
         if len(_DEPTHS_DEV) >= 64:
@@ -1129,7 +1164,7 @@ def plane_sweep(img: torch.Tensor, depth_planes, ki: torch.Tensor, proj: torch.T
     dd = _depths_on(depth_planes, dev)
     D = dd.shape[0]
     out = torch.empty((B, tgt_h, tgt_w, D * C), device=dev, dtype=torch.float32)
-    kid, projd = _up(ki, dev), _up(proj, dev)
+    kid, projd = _up(ki, dev, "ki"), _up(proj, dev, "proj")
     _call("mpiv_plane_sweep", img, _strides(img), B, Hs, Ws, C, kid, projd, dd, D, tgt_h, tgt_w, out, _stream(dev))
     return out
 
@@ -1145,8 +1180,9 @@ def plane_sweep_pose(img: torch.Tensor, depth_planes, ki: torch.Tensor, Ks: torc
     call: B = 1, the result still [1,...]); ki [B,9] on the device, Ks [3,3] (one camera) or
     [B,3,3] with 3x3 blocks contiguous, pose [B,4,4] (or [4,4]) contiguous fp32 on the device.
     The [B,16] proj lands in a scratch buffer kept per device and stream (reused in stream
-    order).  The notebook's dataset calls this once per sample at 224x224x10, where the kernel
-    is ~12 us, so the host path is kept to a handful of torch calls."""
+    order; under a HIP-graph capture in a fresh tensor of the graph's pool).  The notebook's
+    dataset calls this once per sample at 224x224x10, where the kernel is ~12 us, so the host
+    path is kept to a handful of torch calls."""
     _require_depths(depth_planes)
     dev = _dev(img, Ks, pose)
     if img.dim() == 3:
@@ -1167,10 +1203,15 @@ def plane_sweep_pose(img: torch.Tensor, depth_planes, ki: torch.Tensor, Ks: torc
     sid = stream.cuda_stream
     dd = _depths_on(depth_planes, dev, sid)
     D = dd.shape[0]
-    key = (dev.index, sid)
-    scratch = _PROJ_SCRATCH.get(key)
-    if scratch is None or scratch.numel() < B * 16:
-        scratch = _PROJ_SCRATCH[key] = torch.empty(max(B, 8) * 16, device=dev, dtype=torch.float32)
+    if torch.cuda.is_current_stream_capturing():
+        # HIP-graph capture: proj goes to a fresh tensor of the graph's own pool (the memoised scratch is
+        # replaced, and freed, by a later eager call with a larger batch; a replay would write into it)
+        scratch = torch.empty(B * 16, device=dev, dtype=torch.float32)
+    else:
+        key = (dev.index, sid)
+        scratch = _PROJ_SCRATCH.get(key)
+        if scratch is None or scratch.numel() < B * 16:
+            scratch = _PROJ_SCRATCH[key] = torch.empty(max(B, 8) * 16, device=dev, dtype=torch.float32)
     ks_b = 0 if Ks.dim() == 2 else Ks.stride(0)
     out = torch.empty((B, tgt_h, tgt_w, D * C), device=dev, dtype=torch.float32)
     _call("mpiv_plane_sweep_pose", img, cst, B, Hs, Ws, C, ki, Ks, ks_b, pose, scratch, dd, D, tgt_h, tgt_w,
@@ -1190,8 +1231,8 @@ def plane_sweep_padded(img: torch.Tensor, depth_planes, ki: torch.Tensor, proj: 
     D = dd.shape[0]
     out = torch.empty((B, tgt_h, tgt_w, D * C), device=dev, dtype=torch.float32)
     img4 = pad_texels(img)
-    _call("mpiv_plane_sweep_padded", img4, B, Hs, Ws, C, _up(ki, dev), _up(proj, dev), dd, D, tgt_h,
-          tgt_w, out, _stream(dev))
+    _call("mpiv_plane_sweep_padded", img4, B, Hs, Ws, C, _up(ki, dev, "ki"), _up(proj, dev, "proj"), dd, D,
+          tgt_h, tgt_w, out, _stream(dev))
     return out
 
 
@@ -1242,8 +1283,8 @@ def network_input(ref_image, psv_src_images, rel_poses, depth_planes, intrinsics
     for i, pose in enumerate(rel_poses):
         src = psv_src_images[:, :, :, i * 3:(i + 1) * 3]  # a strided channel slice, read in place
         ki, proj = psv_matrices(intrinsics, intrinsics, pose, pin=True)
-        _call("mpiv_plane_sweep_into", src, _strides(src), B, H, W, 3, _up(ki, dev), _up(proj, dev), dd, D, H, W,
-              out[..., 3 + i * D * 3:], H * W * Ctot, Ctot, _stream(dev))
+        _call("mpiv_plane_sweep_into", src, _strides(src), B, H, W, 3, _up(ki, dev, "ki"), _up(proj, dev, "proj"),
+              dd, D, H, W, out[..., 3 + i * D * 3:], H * W * Ctot, Ctot, _stream(dev))
     return out
 
 
@@ -1253,7 +1294,7 @@ def inverse_warp_depthmap(img, depth, ki, proj, tgt_h, tgt_w):
     if tuple(depth.shape) != (B, tgt_h, tgt_w):
         raise RuntimeError(f"depth must be [{B},{tgt_h},{tgt_w}], got {tuple(depth.shape)}")
     out = torch.empty((B, tgt_h, tgt_w, C), device=dev, dtype=torch.float32)
-    _call("mpiv_inverse_warp", img, _strides(img), B, Hs, Ws, C, _up(ki, dev), _up(proj, dev),
+    _call("mpiv_inverse_warp", img, _strides(img), B, Hs, Ws, C, _up(ki, dev, "ki"), _up(proj, dev, "proj"),
           depth, _strides(depth), tgt_h, tgt_w, out, _stream(dev))
     return out
 
@@ -1326,6 +1367,7 @@ def over_composite(rgbas) -> torch.Tensor:
         layers = [t.contiguous() for t in layers]
     ps, cs = _flat_pixels(layers[0])
     n = layers[0].numel() // 4
+    host_under_capture("over_composite's layer pointer table (built on the host per call)")
     ptrs = torch.tensor([t.data_ptr() for t in layers], dtype=torch.int64).to(dev)
     out = torch.empty(tuple(shape[:-1]) + (3,), device=dev, dtype=torch.float32)
     _call("mpiv_over_composite", ptrs, len(layers), n, ps, cs, out, _stream(dev))
@@ -1374,7 +1416,7 @@ def pixel2cam(depth, pixel_coords, intrinsics, is_homogeneous=True):
     rows = 4 if is_homogeneous else 3
     cam = torch.empty((B, rows, H, W), device=dev, dtype=torch.float32)
     _call("mpiv_pixel2cam", depth.contiguous(), pixel_coords.reshape(B, 3, n).contiguous(),
-          _up(ki, dev), B, n, int(bool(is_homogeneous)), cam, _stream(dev))
+          _up(ki, dev, "inverse(intrinsics)"), B, n, int(bool(is_homogeneous)), cam, _stream(dev))
     return cam
 
 
@@ -1399,6 +1441,6 @@ def warp_planes(imgs: torch.Tensor, pixel_coords_trg: torch.Tensor, hom: torch.T
     Ht, Wt = pixel_coords_trg.shape[-3], pixel_coords_trg.shape[-2]
     pts = pixel_coords_trg.reshape(M, Ht * Wt, 3).contiguous()
     coords = torch.empty((M, Ht, Wt, 2), device=dev, dtype=torch.float32)
-    _call("mpiv_plane_coords", pts, M, Ht * Wt, _up(hom.reshape(M, 9), dev), Ht, Wt, coords,
+    _call("mpiv_plane_coords", pts, M, Ht * Wt, _up(hom.reshape(M, 9), dev, "hom"), Ht, Wt, coords,
           _stream(dev))
     return bilinear_sample(imgs, coords.reshape(list(pixel_coords_trg.shape[:-1]) + [2]), channels_last_out=False)

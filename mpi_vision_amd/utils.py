@@ -149,6 +149,8 @@ def mpi_render_view_torch(rgba_layers, tgt_pose, planes, intrinsics):
     if tgt_pose.is_cuda and rgba_layers.is_cuda:  # poses in HBM: the chain runs there too
         homs = _host.render_homographies_device(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
     else:
+        if rgba_layers.is_cuda:
+            _lib.host_under_capture("tgt_pose")  # host poses cannot be part of a captured HIP graph
         homs = _host.render_homographies(tgt_pose, depths.reshape(-1), intrinsics, batch_size,
                                          pin=rgba_layers.is_cuda)
     if torch.is_grad_enabled() and rgba_layers.requires_grad:
