@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MPIV_ABI_VERSION 16
+#define MPIV_ABI_VERSION 17
 
 enum {
     MPIV_OK = 0,
@@ -51,8 +51,10 @@ const char *mpiv_build_id(void);
  * "render_tile", "render_vshare", "chunk_rows", "chunk_flight", "sweep_tile", "sweep_store",
  * "sweep_dlane", "sweep_rows", "sweep_direct", "box_shrink", "bwd_fallback", "bwd_margin",
  * "bwd_gather", "bwd_poll_limit", "bwd_fb_blocks", "bwd_fb_mode", "chunk_strip", "u8_flight", "bwd_group",
- * "netout_geo", "netout_buf", "bwd_overlap", "sweep_band", "sweep_pf", "sweep_soa"; "reset" restores every
- * default; abi.hip documents the values).  Values that
+ * "netout_geo", "netout_buf", "bwd_overlap", "sweep_band", "sweep_pf", "sweep_soa", "chunk_wide"; "reset"
+ * restores every default; abi.hip documents the values).  "chunk_wide" = 1 is a test hook the production
+ * library accepts: mpiv_render_train and mpiv_render_backward[_watched] then take their wide (64-bit tap
+ * address) instantiations at any view size, not only from 2 GiB up (0 = automatic).  Values that
  * select a kernel kept only for A/B measurement return MPIV_ERR_ARG from libmpiv.so (they are
  * compiled into libmpiv_ab.so).  Process-wide; returns MPIV_ERR_ARG for an unknown name. */
 int mpiv_debug_set(const char *name, int value);
@@ -69,6 +71,9 @@ int mpiv_debug_set(const char *name, int value);
  *   "render_packed_u8"                   {H, W, P, V}        (mpiv_render_packed_u8)
  *   "render_packed_f16", "render_packed_f16_ct"  {H, W, P, V} (mpiv_render_packed_f16[_ct])
  *   "render_net_output"                  {B, H, W, P}        (mpiv_render_net_output)
+ *   "render_train"                       {B, H, W, P}        (mpiv_render_train, contiguous MPI)
+ *   "render_backward"                    {B, H, W, P}        (mpiv_render_backward, contiguous MPI, the
+ *                                                            caller's checkpoints: names the chain kernel)
  * Fails while a debug option is set (it reports production routes only). */
 int mpiv_route(const char *entry, const int64_t *args, int nargs, char *name, int name_cap, int64_t *grid_threads);
 
@@ -90,7 +95,13 @@ int mpiv_render(const float *mpi, const int64_t mpi_strides[5], int B, int H, in
  * composited colour before every 8-plane chunk, ckpt [B][ceil(P/8)][H][W] float4 (16-B
  * aligned; chunk 0's slot is unused), which mpiv_render_backward takes instead of
  * recomputing the forward composite.  Needs the in-place layout (16-B texels, planes
- * contiguous per pixel, strides[3] == 4, strides[4] == 1), H, W >= 2 and P <= 796. */
+ * contiguous per pixel, strides[3] == 4, strides[4] == 1), H, W >= 2 and P <= 796.
+ * One view may span any number of bytes: below 2 GiB its taps go through a buffer resource with
+ * 32-bit offsets, from 2 GiB up through 64-bit addresses (the wide instantiation, same bits).
+ * The ceiling per view is the backward's: H*W < 2^26 and P*H*W < 2^31 (32 GiB of fp32 RGBA).
+ * Unchanged: strides[1], strides[2] non-negative, multiples of 4 and below 2^22 texels (2^24
+ * floats) -- the wide arithmetic would not need the 2^22 bound, but it is kept so that both
+ * instantiations accept the same strides. */
 int mpiv_render_train(const float *mpi, const int64_t mpi_strides[5], int B, int H, int W, int P,
                       const float *homs, float *out, float *ckpt, void *stream);
 
@@ -188,7 +199,10 @@ size_t mpiv_render_backward_workspace_size_min(int H, int W, int P);
  * dmpi:    [V,H,W,P,4] contiguous, 16-byte aligned: view v's gradient is written (not
  *          accumulated);
  * workspace: >= mpiv_render_backward_workspace_size(H, W, P) bytes, 256-B aligned.
- * Deterministic (no float atomics); H*W < 2^26, P*H*W < 2^31.
+ * Deterministic (no float atomics).  Limits per view: H*W < 2^26 and P*H*W < 2^31 (32-bit pixel
+ * ids and order keys: 32 GiB of fp32 RGBA); strides[1], strides[2] non-negative and below 2^22
+ * texels.  The byte span of a view is not limited: from 2 GiB up the chain reads its taps through
+ * 64-bit addresses (the wide instantiation, same bits) instead of a buffer resource.
  * A view the tile gather cannot prove complete runs the bucket fallback, whose phases are
  * ordered by tickets (no block needs to be resident: safe beside other streams, RCCL kernels
  * and other processes).  If a fallback wait ever outlasts its poll limit (not expected), that

@@ -95,7 +95,7 @@ _SIGS = {
 EXPORTS = tuple(_SIGS) + ("mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
                           "mpiv_render_backward_abort_flag",
                           "mpiv_render_backward_workspace_size_min", "mpiv_build_id", "mpiv_debug_set")
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _lib = None
 _lib_ab = None
@@ -781,13 +781,22 @@ def render(rgba_layers: torch.Tensor, homs: torch.Tensor) -> torch.Tensor:
 
 def bwd_layout_ok(rgba_layers: torch.Tensor) -> bool:
     """True when mpiv_render_backward reads this [B,H,W,P,4] tensor in place (abi.hip:
-    16-B texels with planes contiguous per pixel, one view below the buffer range)."""
+    16-B texels with planes contiguous per pixel, row and pixel strides below 2^22 texels; a
+    view of 2 GiB or more is read through 64-bit tap addresses, so its span is not limited)."""
     B, H, W, P, C = rgba_layers.shape
     st = rgba_layers.stride()
     if C != 4 or st[4] != 1 or st[3] != 4 or any(s % 4 for s in st[:3]) or st[1] < 0 or st[2] < 0:
         return False
-    rec = ((H - 1) * st[1] + (W - 1) * st[2]) * 4 + 8 * 16
-    return rgba_layers.data_ptr() % 16 == 0 and rec < _KOOB and st[1] // 4 < (1 << 22) and st[2] // 4 < (1 << 22)
+    return rgba_layers.data_ptr() % 16 == 0 and st[1] // 4 < (1 << 22) and st[2] // 4 < (1 << 22)
+
+
+def train_layout_ok(rgba_layers: torch.Tensor) -> bool:
+    """True when mpiv_render_train reads this [B,H,W,P,4] tensor in place and returns checkpoints:
+    bwd_layout_ok's layout with H, W >= 2, the view's homographies in LDS beside the sample slots
+    (P <= 796) and the backward's size ceiling (H*W < 2^26, P*H*W < 2^31)."""
+    B, H, W, P, C = rgba_layers.shape
+    return (bwd_layout_ok(rgba_layers) and H >= 2 and W >= 2 and 4 * 64 * 9 * 16 + P * 36 <= _CHUNK_LDS
+            and H * W < (1 << 26) and P * H * W < (1 << 31))
 
 
 def bwd_flag_offset(H: int, W: int, P: int) -> int:
@@ -804,8 +813,7 @@ def render_train(rgba_layers: torch.Tensor, homs: torch.Tensor):
     B, H, W, P, _ = rgba_layers.shape
     if homs.shape[0] != B or homs.shape[1] != P:
         raise RuntimeError(f"shape mismatch: MPI batch/planes {B}/{P} vs poses/planes {homs.shape[0]}/{homs.shape[1]}")
-    if (B > 1 and rgba_layers.stride(0) == 0) or not chunk_layout_ok(rgba_layers) or \
-            4 * 64 * 9 * 16 + P * 36 > _CHUNK_LDS:
+    if (B > 1 and rgba_layers.stride(0) == 0) or not train_layout_ok(rgba_layers):
         return render(rgba_layers, homs), None
     h = _up(homs, dev, "homs")
     out = torch.empty((B, H, W, 3), device=dev, dtype=torch.float32)

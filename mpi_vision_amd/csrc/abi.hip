@@ -132,6 +132,9 @@ inline unsigned blocks(int64_t n, int per) { return (unsigned)((n + per - 1) / p
 //   render_order=-1|0|1  which tile a block of the sampling kernels (render_rows_kernel, render_u8_kernel,
 //                      render_packed_kernel) renders (render.hip xcd_tile_order): each XCD one band of tile
 //                      rows / automatic (render_tile_order) / every eighth tile, interleaved over the frame
+//   chunk_wide=0|1     test hook: the in-place training readers (mpiv_render_train, mpiv_render_backward)
+//                      take their wide instantiations (64-bit tap addresses, global loads) for views of
+//                      2 GiB or more only (0 = automatic) / at any size (1)
 //   bwd_margin=k       the tile gather's pixel-window margin in 1/64 pixel (default 16);
 //                      negative values make windows miss contributors, which the pair
 //                      count must catch (tests)
@@ -142,7 +145,7 @@ enum DebugOpt { kOptRenderMv, kOptRenderPair, kOptNativeLds, kOptSweepTile, kOpt
                 kOptRenderVshare, kOptChunkRows, kOptSweepRows, kOptChunkFlight, kOptBwdGather, kOptSweepDirect,
                 kOptBwdPollLimit, kOptBwdFbBlocks, kOptBwdFbMode, kOptChunkStrip, kOptU8Flight, kOptBwdGroup,
                 kOptNetoutGeo, kOptNetoutBuf, kOptBwdOverlap, kOptSweepBand, kOptSweepPf, kOptSweepSoa, kOptBwdUnfold,
-                kOptNetoutFg3, kOptRenderSame, kOptRenderColsep, kOptRenderOrder, kNumOpts };
+                kOptNetoutFg3, kOptRenderSame, kOptRenderColsep, kOptRenderOrder, kOptChunkWide, kNumOpts };
 const char* const kOptNames[kNumOpts] = {"render_mv", "render_pair", "render_native_lds",
                                          "sweep_tile", "sweep_store", "box_shrink", "render_chunk", "render_ring",
                                          "render_tile", "bwd_fallback", "bwd_margin", "sweep_dlane",
@@ -150,7 +153,7 @@ const char* const kOptNames[kNumOpts] = {"render_mv", "render_pair", "render_nat
                                          "sweep_direct", "bwd_poll_limit", "bwd_fb_blocks", "bwd_fb_mode",
                                          "chunk_strip", "u8_flight", "bwd_group", "netout_geo", "netout_buf", "bwd_overlap", "sweep_band",
                                          "sweep_pf", "sweep_soa", "bwd_unfold", "netout_fg3",
-                                         "render_same", "render_colsep", "render_order"};
+                                         "render_same", "render_colsep", "render_order", "chunk_wide"};
 #ifndef MPIV_CHUNK_STRIP
 #define MPIV_CHUNK_STRIP 1  // round 4: 0.506 vs 0.64 ms in place (profiles/r04j_strip*_ab.jsonl)
 #endif
@@ -158,9 +161,9 @@ const char* const kOptNames[kNumOpts] = {"render_mv", "render_pair", "render_nat
 #define MPIV_U8_FLIGHT 0
 #endif
 const int kOptDefaults[kNumOpts] = {0, 0, 1, 0, -1, 0, 0, 0, 0, 0, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, MPIV_CHUNK_STRIP,
-                                    MPIV_U8_FLIGHT, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0};
+                                    MPIV_U8_FLIGHT, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0};
 int g_opts[kNumOpts] = {0, 0, 1, 0, -1, 0, 0, 0, 0, 0, 16, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, MPIV_CHUNK_STRIP, MPIV_U8_FLIGHT, 0,
-                        0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0};
+                        0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0};
 
 int opt(DebugOpt o) { return __atomic_load_n(&g_opts[o], __ATOMIC_RELAXED); }
 
@@ -216,6 +219,14 @@ constexpr int kChunkSplit = 1;       // composite phases per chunk (render_chunk
 
 constexpr int64_t kMaxGridX = 2147483647;
 
+// The training entries' ceiling per view (mpiv_render_train, mpiv_render_backward[_watched]): the
+// backward's pixel ids, bucket ids and order keys are 32-bit.  The byte span of a view is not
+// limited: from 2 GiB up the in-place readers take their wide instantiations.
+constexpr const char* kViewTooLarge = "%s: one view is limited to H*W < 2^26 and P*H*W < 2^31 (32 GiB of fp32 RGBA)";
+inline bool view_too_large(int H, int W, int P) {
+    return (int64_t)H * W >= ((int64_t)1 << 26) || (int64_t)P * H * W >= ((int64_t)1 << 31);
+}
+
 }  // namespace
 
 using namespace mpiv;
@@ -246,7 +257,17 @@ int chunk_rows() {
 // launch render_chunk_kernel<CH, SPLIT, R> with the block count of its 64 x 4R tiles
 template <int CH, int SPLIT>
 int launch_chunk(int R, const float* mpi, int64_t vstride, const RenderGeom& g, const ChunkGeom& cg, int B,
-                 const float* homs, float* out, float4* ck, size_t lds, hipStream_t q, const char* nm) {
+                 const float* homs, float* out, float4* ck, size_t lds, hipStream_t q, const char* nm,
+                 bool wide = false) {
+    if constexpr (CH == 8 && SPLIT == 1) {
+        if (wide) {  // a view of 2 GiB or more (mpiv_render_train): the 8 x 16 strips with 64-bit tap addresses
+            const int64_t ns = (int64_t)blocks(g.W, kStripTX) * blocks(g.H, 16) * B;
+            if (ns > kMaxGridX) return fail(MPIV_ERR_ARG, "%s: too many blocks", nm);
+            if (g_route) return note_route(ns, 256, "render_chunk_strip_kernel<16, 2, true>");
+            render_chunk_strip_kernel<16, 2, true><<<(unsigned)ns, 256, lds, q>>>(mpi, vstride, g, cg, B, homs, out, ck);
+            return launched(nm);
+        }
+    }
     const int64_t nb = (int64_t)blocks(g.W, kTileX) * blocks(g.H, kTileY * R) * B;
     if (nb > kMaxGridX) return fail(MPIV_ERR_ARG, "%s: too many blocks", nm);
     const int NT = (opt(kOptChunkFlight) == 4 && R == 1 && SPLIT == 1) ? 4 : 2;
@@ -377,13 +398,16 @@ int mpiv_render_train(const float* mpi, const int64_t st[5], int B, int H, int W
     const int64_t rec = ((int64_t)(H - 1) * st[1] + (int64_t)(W - 1) * st[2]) * 4 + 8 * 16;
     const size_t ch_lds = (size_t)4 * kWave * 9 * 16 + (size_t)P * 36;
     if (st[4] != 1 || st[3] != 4 || st[0] % 4 || st[1] % 4 || st[2] % 4 || st[1] < 0 || st[2] < 0 ||
-        !aligned16(mpi) || !aligned16(ckpt) || rec >= (int64_t)kOOB || st[1] / 4 >= (1 << 22) ||
-        st[2] / 4 >= (1 << 22) || ch_lds > (size_t)kChunkMaxLds)
+        !aligned16(mpi) || !aligned16(ckpt) || st[1] / 4 >= (1 << 22) || st[2] / 4 >= (1 << 22) ||
+        ch_lds > (size_t)kChunkMaxLds)
         return fail(MPIV_ERR_ARG, "%s: rgba_layers must be read in place (16-byte texels, planes contiguous per "
-                    "pixel, one view below 2 GiB, P <= 796)", nm);
-    const ChunkGeom cg{(int)(st[1] / 4), (int)(st[2] / 4), (int)rec};
+                    "pixel, row and pixel strides below 2^22 texels, P <= 796)", nm);
+    if (view_too_large(H, W, P)) return fail(MPIV_ERR_ARG, kViewTooLarge, nm);
+    // a view whose taps reach the buffer unit's out-of-range offset (2 GiB) is read through 64-bit addresses
+    const bool wide = rec >= (int64_t)kOOB || opt(kOptChunkWide) == 1;
+    const ChunkGeom cg{(int)(st[1] / 4), (int)(st[2] / 4), rec < (int64_t)kOOB ? (int)rec : 0};
     return launch_chunk<8, 1>(chunk_rows(), mpi, st[0], make_geom(H, W, P), cg, B, homs, out,
-                              reinterpret_cast<float4*>(ckpt), ch_lds, S(stream), nm);
+                              reinterpret_cast<float4*>(ckpt), ch_lds, S(stream), nm, wide);
 }
 
 int mpiv_pack_planes(const float* mpi, const int64_t st[4], int H, int W, int P, float* packed, void* stream) {
@@ -926,8 +950,10 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     if (st[4] != 1 || st[3] != 4 || st[0] % 4 || st[1] % 4 || st[2] % 4 || !aligned16(mpi))
         return fail(MPIV_ERR_ARG, "%s: rgba_layers must have 16-byte aligned texels with planes contiguous per pixel "
                     "(strides[3] == 4, strides[4] == 1)", nm);
-    if (st[1] < 0 || st[2] < 0 || rec >= (int64_t)kOOB || st[1] / 4 >= (1 << 22) || st[2] / 4 >= (1 << 22))
-        return fail(MPIV_ERR_ARG, "%s: one view's MPI must span less than 2 GiB", nm);
+    if (st[1] < 0 || st[2] < 0 || st[1] / 4 >= (1 << 22) || st[2] / 4 >= (1 << 22))
+        return fail(MPIV_ERR_ARG, "%s: rgba_layers' row and pixel strides must be non-negative and below 2^22 texels", nm);
+    // a view whose taps reach the buffer unit's out-of-range offset (2 GiB) is read through 64-bit addresses
+    const bool wide = rec >= (int64_t)kOOB || opt(kOptChunkWide) == 1;
     // the chain's homographies go to LDS beside its sample slots when they fit (P <= 796),
     // else it reads them from global memory
     const size_t slots_lds = (size_t)4 * kWave * (kBwdCH + 1) * 16;
@@ -938,8 +964,7 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     if (!aligned16(dmpi) || (reinterpret_cast<uintptr_t>(workspace) & 255))
         return fail(MPIV_ERR_ARG, "%s: d rgba_layers must be 16-byte and workspace 256-byte aligned", nm);
     // pixel ids, bucket ids and order keys are 32-bit
-    if ((int64_t)H * W >= ((int64_t)1 << 26) || (int64_t)P * H * W >= ((int64_t)1 << 31))
-        return fail(MPIV_ERR_ARG, "%s: MPI too large for one backward launch", nm);
+    if (view_too_large(H, W, P)) return fail(MPIV_ERR_ARG, kViewTooLarge, nm);
     // plane groups: one (every plane's d samples resident) when the workspace holds it, else
     // groups of bwd_group_planes (mpiv_render_backward_workspace_size / _size_min)
     // Overlapped (round 5, default for views of more than one group): groups of bwd_group_planes in two
@@ -948,7 +973,7 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     // workspace holds two windows (the default workspace does)
     const bool fast2 = H >= 2 && W >= 2;
     const int GPo = bwd_group_planes(H, W, P);
-    const bool overlap = MPIV_AB && opt(kOptBwdOverlap) != 0 && fast2 && GPo < P &&
+    const bool overlap = MPIV_AB && opt(kOptBwdOverlap) != 0 && fast2 && GPo < P && !wide &&
                          ws_bytes >= bwd_layout(H, W, P, GPo, nullptr, nullptr, nullptr, 2);
     const int GP = overlap ? GPo : (opt(kOptBwdGroup) > 0 || ws_bytes < bwd_layout(H, W, P, P, nullptr, nullptr))
                                        ? bwd_group_planes(H, W, P) : P;
@@ -958,7 +983,7 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     const size_t need = bwd_layout(H, W, P, GP, static_cast<char*>(workspace), &ws, &gbuf, overlap ? 2 : 1, &ws2);
     if (ws_bytes < need) return fail(MPIV_ERR_ARG, "%s: workspace too small (%zu < %zu bytes)", nm, ws_bytes, need);
     const RenderGeom g = make_geom(H, W, P);
-    const ChunkGeom cg{(int)(st[1] / 4), (int)(st[2] / 4), (int)rec};
+    const ChunkGeom cg{(int)(st[1] / 4), (int)(st[2] / 4), rec < (int64_t)kOOB ? (int)rec : 0};
     const bool fast = H >= 2 && W >= 2;
     const int64_t HW = (int64_t)H * W;
     {
@@ -976,6 +1001,13 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     const int force = opt(kOptBwdFallback) != 0 || !fast;
     const float margin = (float)opt(kOptBwdMargin) / 64.0f;
     hipStream_t q = S(stream);
+    if (g_route) {  // dry run: the chain kernel of this view (production options)
+        if (!fast)
+            return note_route((int64_t)blocks(W, kTileX) * blocks(H, kTileY), 256,
+                              wide ? "bwd_chain_kernel<0, false, 1, true>" : "bwd_chain_kernel<0, false, 1>");
+        return note_route((int64_t)blocks(W, kStripTX) * blocks(H, 8), 256,
+                          wide ? "bwd_chain_strip_kernel<8, true>" : "bwd_chain_strip_kernel<8>");
+    }
     // fallback grid: at most the blocks that fit at once, <= 4 per CU (more would only wait for
     // tickets; fewer resident ones still complete); queried once per device (racing first calls
     // store the same values; the block count is published with release after the clock rate and
@@ -1076,6 +1108,24 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
         }
         // no second stream: the sequential schedule below on the first window
     }
+    // the strip forward that writes a view's checkpoints into the workspace (no checkpoints from the
+    // caller), and the strip chain over chunks [c_lo, c_hi): narrow or wide instantiation by the view
+    auto forward_ckpt = [&](const float* mv, const float* hv, float* frame) {
+        const unsigned fb = blocks(W, kStripTX) * blocks(H, 16);
+        const size_t flds = (size_t)chunk_slot_floats<8, 1>() * 4 + (h_lds ? (size_t)P * 36 : 0);
+        if (wide)
+            render_chunk_strip_kernel<16, 2, true><<<fb, 256, flds, q>>>(mv, 0, g, cg, 1, hv, frame, ws.ckpt, h_lds);
+        else
+            render_chunk_strip_kernel<16, 2><<<fb, 256, flds, q>>>(mv, 0, g, cg, 1, hv, frame, ws.ckpt, h_lds);
+    };
+    auto chain_strip = [&](const float* mv, const float* hv, const float* dv, const float4* ckv, const BwdWs& wg,
+                           int c_lo, int c_hi) {
+        const unsigned nb = blocks(W, kStripTX) * blocks(H, 8);
+        if (wide)
+            bwd_chain_strip_kernel<8, true><<<nb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, ckv, wg, h_lds, c_lo, c_hi, gbuf);
+        else
+            bwd_chain_strip_kernel<8><<<nb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, ckv, wg, h_lds, c_lo, c_hi, gbuf);
+    };
     for (int v = 0; v < V; ++v) {
         const float* hv = homs + (int64_t)v * P * 9;
         const float* dv = dout + (int64_t)v * HW * 3;
@@ -1086,10 +1136,7 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
         if (G > 1) {  // several plane groups, back to front (fast recipe: H, W >= 2 here, P * H * W > 2^25)
             const float4* ckv = ck;
             if (!ckv) {  // the checkpoints from a forward pass into the workspace (frame into gbuf, unused)
-                const unsigned fb = blocks(W, kStripTX) * blocks(H, 16);
-                const size_t flds = (size_t)chunk_slot_floats<8, 1>() * 4 + (h_lds ? (size_t)P * 36 : 0);
-                render_chunk_strip_kernel<16, 2><<<fb, 256, flds, q>>>(mv, 0, g, cg, 1, hv, reinterpret_cast<float*>(gbuf),
-                                                                      ws.ckpt, h_lds);
+                forward_ckpt(mv, hv, reinterpret_cast<float*>(gbuf));
                 ckv = ws.ckpt;
             }
             if (!force)  // the planes' inverses computed inside (one launch fewer)
@@ -1099,8 +1146,7 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
                 const int p_lo = grp * GP, p_hi = std::min(P, p_lo + GP);
                 BwdWs wg = ws;
                 wg.ds_p0 = p_lo;  // the window holds the group's d samples: planes p_lo .. p_hi-1
-                bwd_chain_strip_kernel<8><<<blocks(W, kStripTX) * blocks(H, 8), 256, chain_lds, q>>>(
-                    mv, g, cg, hv, dv, ckv, wg, h_lds, p_lo / kBwdCH, (p_hi + kBwdCH - 1) / kBwdCH, gbuf);
+                chain_strip(mv, hv, dv, ckv, wg, p_lo / kBwdCH, (p_hi + kBwdCH - 1) / kBwdCH);
                 if (!force)
                     bwd_gather_kernel<false><<<(unsigned)(ntiles * blocks(p_hi - p_lo, kGPl)), kGThreads, 0, q>>>(
                         g, hv, wg, gv, margin, p_lo, p_hi - p_lo);
@@ -1121,20 +1167,22 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
             bwd_box_kernel<true><<<blocks((int64_t)P * ntiles, 256), 256, 0, q>>>(
                 g, hv, ws.inv, (int)ntiles, tiles_x, margin, ws.box, (double)W / (H - 1), (double)H / (W - 1), ws,
                 v == 0 ? 2 : 1);
-        if (!ck && fast && R == 1 && opt(kOptChunkStrip) == 1) {
+        // (a wide view always takes the strip kernels: the only wide instantiations of the fast recipe)
+        if (!ck && fast && ((R == 1 && opt(kOptChunkStrip) == 1) || wide)) {
             // no checkpoints: a strip forward pass writes them into the workspace (its frame into
             // this view's d MPI, which the gather / fallback overwrite), then the one-pass chain --
             // 0.6 + 2.4 ms against 3.0-3.1 for the two-pass chain
-            const unsigned fb = blocks(W, kStripTX) * blocks(H, 16);
-            const size_t flds = (size_t)chunk_slot_floats<8, 1>() * 4 + (h_lds ? (size_t)P * 36 : 0);
-            render_chunk_strip_kernel<16, 2><<<fb, 256, flds, q>>>(mv, 0, g, cg, 1, hv, reinterpret_cast<float*>(gv),
-                                                                  ws.ckpt, h_lds);
+            forward_ckpt(mv, hv, reinterpret_cast<float*>(gv));
             ck = ws.ckpt;
         }
 #define MPIV_CHAIN(CKB, RR)                                                                                  \
     bwd_chain_kernel<1, CKB, RR><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, CKB ? ck : nullptr, ws, h_lds)
-        if (!fast)
+        if (!fast && wide)
+            bwd_chain_kernel<0, false, 1, true><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
+        else if (!fast)
             bwd_chain_kernel<0, false, 1><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
+        else if (wide)
+            chain_strip(mv, hv, dv, ck, ws, 0, (P + 7) / 8);
 #if MPIV_AB  // R rows per wave: measured slower
         else if (ck && R == 4) MPIV_CHAIN(true, 4);
         else if (ck && R == 2) MPIV_CHAIN(true, 2);
@@ -1148,9 +1196,7 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
                                                                                                 gbuf);
 #endif
         else if (ck && opt(kOptChunkStrip))  // 8 x 8 strips, vertical tap reuse
-            bwd_chain_strip_kernel<8><<<blocks(W, kStripTX) * blocks(H, 8), 256, chain_lds, q>>>(mv, g, cg, hv, dv, ck,
-                                                                                              ws, h_lds, 0, (P + 7) / 8,
-                                                                                              gbuf);
+            chain_strip(mv, hv, dv, ck, ws, 0, (P + 7) / 8);
         else if (ck) MPIV_CHAIN(true, 1);
         else MPIV_CHAIN(false, 1);
 #undef MPIV_CHAIN
@@ -2210,6 +2256,11 @@ int mpiv_route(const char* entry, const int64_t* a, int na, char* name, int name
     } else if (strcmp(entry, "render_train") == 0 && na == 4) {
         const int64_t P = a[3], st[5] = {a[1] * a[2] * P * 4, a[2] * P * 4, P * 4, 4, 1};
         rc = mpiv_render_train(d, st, (int)a[0], (int)a[1], (int)a[2], (int)P, d, d, d, nullptr);
+    } else if (strcmp(entry, "render_backward") == 0 && na == 4) {  // dense strides, the caller's checkpoints
+        const int64_t P = a[3], st[5] = {a[1] * a[2] * P * 4, a[2] * P * 4, P * 4, 4, 1};
+        const float* ck = a[1] >= 2 && a[2] >= 2 ? d : nullptr;  // (degenerate frames keep no checkpoints)
+        rc = mpiv_render_backward(d, st, (int)a[0], (int)a[1], (int)a[2], (int)P, d, d, ck, d, d,
+                                  mpiv_render_backward_workspace_size((int)a[1], (int)a[2], (int)P), nullptr);
     } else if (strcmp(entry, "render_packed_u8") == 0 && na == 4) {
         rc = render_u8_impl(reinterpret_cast<const uint32_t*>(d), (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d,
                             (int)a[3], d, false, nullptr);

@@ -164,7 +164,8 @@ __device__ __forceinline__ void bwd_pos(const float* h, float fx, float fy, cons
 // R rows per wave (render_chunk.hip's row grouping): rows y0 .. y0+R-1 of the wave's 64
 // columns with the chunk loop outside the row loop (row r+1's north taps come from L1/L2);
 // rows past the frame (nrows < R, wave-uniform) re-sample the last row, uncounted and unstored.
-template <int MODE, bool CK, int R>
+// WIDE: a view of 2 GiB or more, taps through issue_taps_chunk_wide (a separate instantiation).
+template <int MODE, bool CK, int R, bool WIDE = false>
 __device__ __forceinline__ void bwd_chain_wave(const float* __restrict__ view, const RenderGeom& g,
                                                const ChunkGeom& cg, const float* __restrict__ hs,
                                                f32x4* __restrict__ slot, int tx0, int y0, int nrows_, int lane,
@@ -190,7 +191,11 @@ __device__ __forceinline__ void bwd_chain_wave(const float* __restrict__ view, c
         const int xs = tx0 + k * PPS + i;
         float px, py;
         bwd_pos<MODE>(hh, (float)xs, (float)(y0 + min(r, nrows - 1)), g, px, py);
-        const int nt = issue_taps_chunk(rsrc(c), g, cg, j, c * CH + j < g.P, px, py, ts);
+        int nt;
+        if constexpr (WIDE)
+            nt = issue_taps_chunk_wide(view + (int64_t)c * CH * 4, g, cg, j, c * CH + j < g.P, px, py, ts);
+        else
+            nt = issue_taps_chunk(rsrc(c), g, cg, j, c * CH + j < g.P, px, py, ts);
         if (cnt && xs < g.W && r < nrows) ntap += nt;
     };
     auto put = [&](int k, const ChunkTaps& ts) { slot[(k * PPS + i) * (CH + 1) + j] = blend_chunk(ts); };
@@ -340,7 +345,7 @@ __device__ __forceinline__ void bwd_chain_wave(const float* __restrict__ view, c
 // Dynamic LDS: 4 per-wave sample slots (64 x (CH+1) float4) + the view's P homographies.
 // MODE 0: generic recipe (H or W < 2); 1: fast recipe, the tile's division proof picks the
 // unguarded path.
-template <int MODE, bool CK, int R>
+template <int MODE, bool CK, int R, bool WIDE = false>
 __global__ __launch_bounds__(256, R == 1 ? 1 : 4) void bwd_chain_kernel(const float* __restrict__ view, RenderGeom g, ChunkGeom cg,
                                                            const float* __restrict__ homs,
                                                            const float* __restrict__ dout,
@@ -370,11 +375,11 @@ __global__ __launch_bounds__(256, R == 1 ? 1 : 4) void bwd_chain_kernel(const fl
     const int nrows = min(R, g.H - y);
     f32x4* slot = slots + wave * kWave * (kBwdCH + 1);
     if (MODE == 0)
-        bwd_chain_wave<0, CK, R>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
+        bwd_chain_wave<0, CK, R, WIDE>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
     else if (proven)
-        bwd_chain_wave<2, CK, R>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
+        bwd_chain_wave<2, CK, R, WIDE>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
     else
-        bwd_chain_wave<1, CK, R>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
+        bwd_chain_wave<1, CK, R, WIDE>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
 }
 
 // The chain fed the forward's checkpoints, as 8 x 8 strips with vertical tap reuse
@@ -386,7 +391,8 @@ __global__ __launch_bounds__(256, R == 1 ? 1 : 4) void bwd_chain_kernel(const fl
 // Chunks [c_lo, c_hi) only (a plane group, mpiv_render_backward: groups back to front so the
 // d samples of one group at a time fit the workspace): g starts from dout for the top group
 // (c_hi == n) and from gbuf otherwise, and leaves in gbuf for the group below (c_lo > 0).
-template <int MODE, int SR>
+// WIDE: a view of 2 GiB or more, taps through issue_taps_strip_wide (a separate instantiation).
+template <int MODE, int SR, bool WIDE = false>
 __device__ __forceinline__ void bwd_chain_wave_strip(const float* __restrict__ view, const RenderGeom& g,
                                                      const ChunkGeom& cg, const float* __restrict__ hs,
                                                      f32x4* __restrict__ slot, int sx0, int sy0, int lane,
@@ -415,8 +421,13 @@ __device__ __forceinline__ void bwd_chain_wave_strip(const float* __restrict__ v
         const int ys = sy0 + k;
         float px, py;
         bwd_pos<MODE>(hh, fx, (float)min(ys, g.H - 1), g, px, py);
-        const int nt = issue_taps_strip(make_rsrc(view + (int64_t)c * CH * 4, cg.rec_bytes), g, cg, j, c * CH + j < g.P,
-                                        px, py, kstride, prev_key, can_share, t);
+        int nt;
+        if constexpr (WIDE)
+            nt = issue_taps_strip_wide(view + (int64_t)c * CH * 4, g, cg, j, c * CH + j < g.P, px, py, kstride,
+                                       prev_key, can_share, t);
+        else
+            nt = issue_taps_strip(make_rsrc(view + (int64_t)c * CH * 4, cg.rec_bytes), g, cg, j, c * CH + j < g.P,
+                                  px, py, kstride, prev_key, can_share, t);
         if (cnt && col_in && ys < g.H) ntap += nt;
     };
     StripTaps A, B;
@@ -536,7 +547,7 @@ __device__ __forceinline__ void bwd_chain_wave_strip(const float* __restrict__ v
 
 // One block = 4 waves = a 32 x SR output tile (wave w: the 8 x SR strip at column 8w); LDS and
 // h_lds as bwd_chain_kernel.  Fast recipe only (MODE 1 / 2 by the tile's division proof).
-template <int SR>
+template <int SR, bool WIDE = false>
 __global__ __launch_bounds__(256, 1) void bwd_chain_strip_kernel(const float* __restrict__ view, RenderGeom g,
                                                                  ChunkGeom cg, const float* __restrict__ homs,
                                                                  const float* __restrict__ dout,
@@ -589,9 +600,9 @@ __global__ __launch_bounds__(256, 1) void bwd_chain_strip_kernel(const float* __
     }
     f32x4* slot = slots + wave * kWave * (kBwdCH + 1);
     if (proven)
-        bwd_chain_wave_strip<2, SR>(view, g, cg, hs, slot, sx0, ty0, lane, dout, ck, ws, c_lo, c_hi, gbuf);
+        bwd_chain_wave_strip<2, SR, WIDE>(view, g, cg, hs, slot, sx0, ty0, lane, dout, ck, ws, c_lo, c_hi, gbuf);
     else
-        bwd_chain_wave_strip<1, SR>(view, g, cg, hs, slot, sx0, ty0, lane, dout, ck, ws, c_lo, c_hi, gbuf);
+        bwd_chain_wave_strip<1, SR, WIDE>(view, g, cg, hs, slot, sx0, ty0, lane, dout, ck, ws, c_lo, c_hi, gbuf);
 }
 
 // ---- 2. gather: per-texel sums in the reference's order ------------------------------

@@ -95,6 +95,39 @@ __device__ __forceinline__ int issue_taps_chunk(__amdgpu_buffer_rsrc_t r, const 
     return ((int)x0 + (int)x1) * ((int)y0 + (int)y1);
 }
 
+// WIDE views (one view spans 2 GiB or more, beyond a buffer resource's 32-bit offsets): a tap's
+// address is the 64-bit sum of the chunk base and ((int64)iy*row_t + (int64)ix*pix_t + jt) texels --
+// no __mul24, no wrap -- and the tap is a 16-byte global load executed only by the lanes whose tap
+// indices passed the image test (and whose plane exists): every other lane keeps +0 and touches no
+// memory, the contract the buffer unit's range check gives the narrow kernels.  A tap inside the
+// image is always loaded, whatever its weight.
+__device__ __forceinline__ f32x4 load_tap_wide(const float* __restrict__ base, int64_t off, bool ok) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (ok) v = *reinterpret_cast<const f32x4*>(base + off);  // the address is formed from checked indices only
+    return v;
+}
+
+// issue_taps_chunk for a wide view; base: the chunk's first texel of pixel (0, 0)
+__device__ __forceinline__ int issue_taps_chunk_wide(const float* __restrict__ base, const RenderGeom& g,
+                                                     const ChunkGeom& cg, int jt, bool live, float px, float py,
+                                                     ChunkTaps& t) {
+    const float fx0 = floorf(px), fy0 = floorf(py);
+    t.wx = px - fx0;
+    t.wy = py - fy0;
+    const int ix = (int)__builtin_amdgcn_fmed3f(fx0, -2.0f, (float)g.W);
+    const int iy = (int)__builtin_amdgcn_fmed3f(fy0, -2.0f, (float)g.H);
+    const bool x0 = (unsigned)ix < (unsigned)g.W, x1 = (unsigned)(ix + 1) < (unsigned)g.W;
+    const bool y0 = live && (unsigned)iy < (unsigned)g.H, y1 = live && (unsigned)(iy + 1) < (unsigned)g.H;
+    // floats from the chunk base to the NW tap: |iy * row_t|, |ix * pix_t| < 2^45, exact in 64 bits
+    const int64_t off = ((int64_t)iy * cg.row_t + (int64_t)ix * cg.pix_t + jt) * 4;
+    const int64_t pf = (int64_t)cg.pix_t * 4, rf = (int64_t)cg.row_t * 4;
+    t.a = load_tap_wide(base, off, x0 && y0);
+    t.b = load_tap_wide(base, off + pf, x1 && y0);
+    t.c = load_tap_wide(base, off + rf, x0 && y1);
+    t.d = load_tap_wide(base, off + rf + pf, x1 && y1);
+    return ((int)x0 + (int)x1) * ((int)y0 + (int)y1);
+}
+
 // LDS: [4 waves][64 / SPLIT pixels][CH + 1] float4 sample slots (one pad texel per pixel
 // row), then the view's P homographies (9 floats each).  The pad makes both access shapes
 // bank-conflict free with IMMEDIATE offsets: a sub-step's ds_write_b128 covers CH
@@ -323,6 +356,32 @@ __device__ __forceinline__ int issue_taps_strip(__amdgpu_buffer_rsrc_t r, const 
     return ((int)x0 + (int)x1) * ((int)y0 + (int)y1);
 }
 
+// issue_taps_strip for a wide view (issue_taps_chunk_wide's addressing and loads; the same keys,
+// sharing and count)
+__device__ __forceinline__ int issue_taps_strip_wide(const float* __restrict__ base, const RenderGeom& g,
+                                                     const ChunkGeom& cg, int jt, bool live, float px, float py,
+                                                     int kstride, int prev_key, bool can_share, StripTaps& t) {
+    const float fx0 = floorf(px), fy0 = floorf(py);
+    t.wx = px - fx0;
+    t.wy = py - fy0;
+    const int ix = (int)__builtin_amdgcn_fmed3f(fx0, -2.0f, (float)g.W);
+    const int iy = (int)__builtin_amdgcn_fmed3f(fy0, -2.0f, (float)g.H);
+    const bool x0 = (unsigned)ix < (unsigned)g.W, x1 = (unsigned)(ix + 1) < (unsigned)g.W;
+    const bool y0 = live && (unsigned)iy < (unsigned)g.H, y1 = live && (unsigned)(iy + 1) < (unsigned)g.H;
+    const int64_t off = ((int64_t)iy * cg.row_t + (int64_t)ix * cg.pix_t + jt) * 4;
+    const int64_t pf = (int64_t)cg.pix_t * 4, rf = (int64_t)cg.row_t * 4;
+    t.key = iy * kstride + ix;
+    t.sh = can_share && t.key == prev_key + kstride;
+    t.c = load_tap_wide(base, off + rf, x0 && y1);
+    t.d = load_tap_wide(base, off + rf + pf, x1 && y1);
+    t.own = __builtin_amdgcn_ballot_w64(!t.sh) != 0;
+    if (t.own) {  // wave-uniform: some lane needs its own north taps
+        t.a = load_tap_wide(base, off, !t.sh && x0 && y0);
+        t.b = load_tap_wide(base, off + pf, !t.sh && x1 && y0);
+    }
+    return ((int)x0 + (int)x1) * ((int)y0 + (int)y1);
+}
+
 // the blended sample of a strip row; pc, pd: the previous row's south taps of this lane
 __device__ __forceinline__ f32x4 blend_strip(const StripTaps& t, const f32x4& pc, const f32x4& pd) {
     ChunkTaps u;
@@ -345,7 +404,8 @@ __device__ __forceinline__ f32x4 blend_strip(const StripTaps& t, const f32x4& pc
 
 // SR strip rows (8 or 16: a chunk's sub-steps, one composite phase per 8 rows) and a ring of
 // NT rows in flight (row k + NT - 1 issued while row k blends, running on into the next chunk).
-template <bool GUARD, int SR, int NT>
+// WIDE: the taps through issue_taps_strip_wide (a separate instantiation: the narrow one is unchanged).
+template <bool GUARD, int SR, int NT, bool WIDE = false>
 __device__ __forceinline__ void render_chunk_wave_strip(const float* __restrict__ view, const RenderGeom& g,
                                                         const ChunkGeom& cg, const float* __restrict__ hs,
                                                         f32x4* __restrict__ slot, int sx0, int sy0, int lane,
@@ -367,8 +427,12 @@ __device__ __forceinline__ void render_chunk_wave_strip(const float* __restrict_
     auto issue = [&](int c, int k, const float* hh, int prev_key, bool can_share, StripTaps& t) {
         float px, py;
         chunk_pos<GUARD>(hh, fx, (float)min(sy0 + k, g.H - 1), g, px, py);
-        issue_taps_strip(make_rsrc(view + (int64_t)c * CH * 4, cg.rec_bytes), g, cg, j, c * CH + j < g.P, px, py,
-                         kstride, prev_key, can_share, t);
+        if constexpr (WIDE)
+            issue_taps_strip_wide(view + (int64_t)c * CH * 4, g, cg, j, c * CH + j < g.P, px, py, kstride, prev_key,
+                                  can_share, t);
+        else
+            issue_taps_strip(make_rsrc(view + (int64_t)c * CH * 4, cg.rec_bytes), g, cg, j, c * CH + j < g.P, px, py,
+                             kstride, prev_key, can_share, t);
     };
     StripTaps T[NT];
     f32x4 sc = {0.f, 0.f, 0.f, 0.f}, sd = sc;  // the previous row's south taps
@@ -442,8 +506,8 @@ constexpr int kStripTX = 32;  // block tile width of the strip kernels (4 strips
 
 // One block = 4 waves = a 32 x SR output tile of one view (wave w: the 8 x SR strip at column
 // 8w); XCD-aware (tile, view) order, tile-level division proof.  Dynamic LDS as
-// render_chunk_kernel<8, 1, 1>.
-template <int SR, int NT>
+// render_chunk_kernel<8, 1, 1>.  WIDE: a view of 2 GiB or more (64-bit tap addresses, global loads).
+template <int SR, int NT, bool WIDE = false>
 __global__ __launch_bounds__(256, 3) void render_chunk_strip_kernel(const float* __restrict__ mpi, int64_t view_stride,
                                                                     RenderGeom g, ChunkGeom cg, int V,
                                                                     const float* __restrict__ homs,
@@ -500,10 +564,10 @@ __global__ __launch_bounds__(256, 3) void render_chunk_strip_kernel(const float*
             cr[hh] = r0; cgr[hh] = g0; cb[hh] = b0;
         }
     } else if (proven)
-        render_chunk_wave_strip<false, SR, NT>(view, g, cg, hs, slot, sx0, ty0, lane, cr, cgr, cb, ck, HW,
+        render_chunk_wave_strip<false, SR, NT, WIDE>(view, g, cg, hs, slot, sx0, ty0, lane, cr, cgr, cb, ck, HW,
                                                8 * (int64_t)g.W, nhk);
     else
-        render_chunk_wave_strip<true, SR, NT>(view, g, cg, hs, slot, sx0, ty0, lane, cr, cgr, cb, ck, HW,
+        render_chunk_wave_strip<true, SR, NT, WIDE>(view, g, cg, hs, slot, sx0, ty0, lane, cr, cgr, cb, ck, HW,
                                               8 * (int64_t)g.W, nhk);
 #pragma unroll
     for (int hh = 0; hh < SR / 8; ++hh) {
