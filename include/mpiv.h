@@ -230,6 +230,28 @@ int *mpiv_render_backward_abort_flag(int device);
  * does): a checker for tests and debug runs, not for the training loop. */
 int mpiv_render_backward_status(const void *workspace, int H, int W, int P, int *aborted_views, void *stream);
 
+/* mpiv_render_backward that also returns d(mpi_render_view_torch)/d(homographies): dhoms [V][P][9]
+ * (4-byte aligned, written, not accumulated), the adjoint of the bilinear sampler w.r.t. the sample
+ * position, of the normalisation and of the projective division, summed over the frame
+ * (render_bwd_cam.hip).  The per-sample terms are the reference's to the bit; the frame sum has a fixed
+ * order of its own (no float atomics), so the result is bit-reproducible and independent of the plane
+ * groups, the checkpoints, the workspace size and the stream.  The chain from dhoms to tgt_pose, planes
+ * and intrinsics is the caller's (mpi_vision_amd._host.render_homographies_autograd).
+ * dmpi:     as in mpiv_render_backward (same schedule, same bits), or NULL for a fixed MPI: then only
+ *           the over-composite adjoint and the camera kernels run -- no gather, check or fallback;
+ * watched:  non-zero: report an aborted view as mpiv_render_backward_watched does;
+ * workspace: >= mpiv_render_backward_cam_workspace_size_min(H, W, P) bytes, 256-B aligned; the fastest
+ *           schedule from mpiv_render_backward_cam_workspace_size(H, W, P).  The first bytes are laid
+ *           out as mpiv_render_backward's (mpiv_render_backward_status reads them).
+ * Non-finite texels, homographies or gradients: no fault; one NaN sample makes its plane's nine sums
+ * NaN, as in the reference. */
+int mpiv_render_backward_cam(const float *mpi, const int64_t mpi_strides[5], int V, int H, int W, int P,
+                             const float *homs, const float *dout, const float *ckpt, float *dmpi,
+                             float *dhoms, void *workspace, size_t workspace_bytes, int watched,
+                             void *stream);
+size_t mpiv_render_backward_cam_workspace_size(int H, int W, int P);
+size_t mpiv_render_backward_cam_workspace_size_min(int H, int W, int P);
+
 /* ---- MPI assembly from the network output ------------------------------- */
 
 /* mpi_from_net_output (fast-torch-stereo-vision.ipynb cell 10 L79-111): the network's

@@ -247,6 +247,41 @@ def render_homographies_torch(pose: torch.Tensor, depths: torch.Tensor, intrinsi
     return H.permute(1, 0, 2, 3).reshape(batch, P, 9).contiguous()
 
 
+def render_homographies_autograd(pose: torch.Tensor, depths: torch.Tensor, intrinsics: torch.Tensor,
+                                 batch: int) -> torch.Tensor:
+    """render_homographies_torch WITHOUT the detach: the reference's op chain on CPU in fp32, with its
+    materialised repeats, as a node of the autograd graph of `pose`, `depths` and `intrinsics` -- so
+    d render / d homographies (render_bwd_cam.hip) flows on to tgt_pose, planes and intrinsics through
+    the very torch ops the reference differentiates.  Values equal render_homographies bit for bit.
+    Returns a [B, P, 9] fp32 CPU tensor.
+
+    A device tensor comes to the host through `.cpu()` (differentiable: its gradient returns to the
+    device), which costs one blocking device-to-host copy per call and device tensor -- the pose, and
+    the depths and intrinsics if they live there; the no-gradient route (render_homographies_device)
+    has none.  Under a HIP-graph capture that copy cannot be recorded: raises (_lib.host_under_capture)
+    before anything is launched."""
+    from . import _lib
+    if torch.cuda.is_available():
+        _lib.host_under_capture("the camera gradient's homography chain (tgt_pose, planes, intrinsics)")
+
+    def host(x):
+        return x.to(device=_CPU, dtype=_F32)
+
+    pose, K = host(pose), host(intrinsics)
+    P = depths.shape[0]
+    d = host(depths).reshape(P, 1).repeat(1, batch)
+    rot = pose[:, :3, :3].unsqueeze(0).repeat(P, 1, 1, 1)
+    t = pose[:, :3, 3:].unsqueeze(0).repeat(P, 1, 1, 1)
+    n_hat = torch.tensor([0.0, 0.0, 1.0], dtype=_F32).reshape(1, 1, 1, 3).repeat(P, batch, 1, 1)
+    a = -d.reshape(P, batch, 1, 1)
+    # (k_s and k_t are two repeats of the intrinsics, as in planar_transform_torch, utils.py:225-226:
+    # one shared repeat would add the two gradients per plane before the sum over the planes)
+    K = K.expand(batch, 3, 3)
+    k_s, k_t = K.unsqueeze(0).repeat(P, 1, 1, 1), K.unsqueeze(0).repeat(P, 1, 1, 1)
+    H = inv_homography(k_s, k_t, rot, t, n_hat, a)  # [P, B, 3, 3]
+    return H.permute(1, 0, 2, 3).reshape(batch, P, 9).contiguous()
+
+
 def _cpu32_together(*ts: torch.Tensor):
     """fp32 CPU copies of several tensors with ONE device-to-host transfer when any of them
     lives on a device (the PSV drop-in's caller keeps K and the pose on the GPU, ipynb cell 8

@@ -92,9 +92,17 @@ _SIGS = {
     "mpiv_render_packed_f16": [_vp, _int, _int, _int, _vp, _int, _vp, _vp],
     "mpiv_render_packed_f16_ct": [_vp, _int, _int, _int, _int, _int, _int, _vp, _int, _vp, _vp],
 }
-EXPORTS = tuple(_SIGS) + ("mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
+# mpiv_render_backward_cam (render_bwd_cam.hip): bound like the entries above.  It is listed on its own
+# because tests/stream_cases.py holds one replay case per _SIGS entry; this entry's side-stream and
+# graph-replay cases are in tests/test_camgrad_gpu.py.
+_SIGS_CAM = {
+    "mpiv_render_backward_cam": [_vp, _c_i64p, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t,
+                                 _int, _vp],
+}
+EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + ("mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
                           "mpiv_render_backward_abort_flag",
-                          "mpiv_render_backward_workspace_size_min", "mpiv_build_id", "mpiv_debug_set")
+                          "mpiv_render_backward_workspace_size_min", "mpiv_render_backward_cam_workspace_size",
+                          "mpiv_render_backward_cam_workspace_size_min", "mpiv_build_id", "mpiv_debug_set")
 ABI_VERSION = 17
 
 _lib = None
@@ -153,7 +161,7 @@ def _open(path: str, check_id: bool):
                            "(python -c 'import __graft_entry__ as g; g.build()')")
     L.mpiv_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int]
     L.mpiv_debug_set.restype = ctypes.c_int
-    for name, args in _SIGS.items():
+    for name, args in (*_SIGS.items(), *_SIGS_CAM.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int
@@ -163,6 +171,9 @@ def _open(path: str, check_id: bool):
     L.mpiv_render_backward_workspace_size.restype = ctypes.c_size_t
     L.mpiv_render_backward_workspace_size_min.argtypes = [_int, _int, _int]
     L.mpiv_render_backward_workspace_size_min.restype = ctypes.c_size_t
+    for fn in (L.mpiv_render_backward_cam_workspace_size, L.mpiv_render_backward_cam_workspace_size_min):
+        fn.argtypes = [_int, _int, _int]
+        fn.restype = ctypes.c_size_t
     L.mpiv_render_backward_abort_flag.argtypes = [_int]
     L.mpiv_render_backward_abort_flag.restype = ctypes.c_void_p
     if L.mpiv_abi_version() != ABI_VERSION:
@@ -805,15 +816,16 @@ def bwd_flag_offset(H: int, W: int, P: int) -> int:
     return 2 * 64 * 8  # the two pair counters (64 slots of 8 B each) precede it (round 4 layout)
 
 
-def render_train(rgba_layers: torch.Tensor, homs: torch.Tensor):
+def render_train(rgba_layers: torch.Tensor, homs: torch.Tensor, broadcast_in_place: bool = False):
     """The forward for training: (frames [B,H,W,3], checkpoints [B,ceil(P/8),H,W,4]) from
     mpiv_render_train -- frames bit-identical to render() -- or (render(), None) when the
-    layout is not read in place (a broadcast batch renders from one packed copy instead)."""
+    layout is not read in place (a broadcast batch renders from one packed copy instead, unless
+    broadcast_in_place: the camera gradient's backward wants the checkpoints of every view)."""
     dev = _dev(rgba_layers)
     B, H, W, P, _ = rgba_layers.shape
     if homs.shape[0] != B or homs.shape[1] != P:
         raise RuntimeError(f"shape mismatch: MPI batch/planes {B}/{P} vs poses/planes {homs.shape[0]}/{homs.shape[1]}")
-    if (B > 1 and rgba_layers.stride(0) == 0) or not train_layout_ok(rgba_layers):
+    if (B > 1 and rgba_layers.stride(0) == 0 and not broadcast_in_place) or not train_layout_ok(rgba_layers):
         return render(rgba_layers, homs), None
     h = _up(homs, dev, "homs")
     out = torch.empty((B, H, W, 3), device=dev, dtype=torch.float32)
@@ -842,13 +854,18 @@ def render_backward_status(workspace: torch.Tensor, H: int, W: int, P: int) -> i
 _BWD_WS: dict = {}
 
 
-def _bwd_ws_sizes(L, H: int, W: int, P: int):
-    """(minimum, fastest) workspace bytes of mpiv_render_backward for one H x W x P view, memoised."""
-    key = (L._name, H, W, P, _DEBUG_GEN)  # (the sizes follow debug options such as bwd_group)
+def _bwd_ws_sizes(L, H: int, W: int, P: int, cam: bool = False):
+    """(minimum, fastest) workspace bytes of mpiv_render_backward (cam: mpiv_render_backward_cam) for one
+    H x W x P view, memoised."""
+    key = (L._name, H, W, P, _DEBUG_GEN, cam)  # (the sizes follow debug options such as bwd_group)
     v = _BWD_WS.get(key)
     if v is None:
-        v = _BWD_WS[key] = (L.mpiv_render_backward_workspace_size_min(H, W, P),
-                            L.mpiv_render_backward_workspace_size(H, W, P))
+        if cam:
+            v = (L.mpiv_render_backward_cam_workspace_size_min(H, W, P),
+                 L.mpiv_render_backward_cam_workspace_size(H, W, P))
+        else:
+            v = (L.mpiv_render_backward_workspace_size_min(H, W, P), L.mpiv_render_backward_workspace_size(H, W, P))
+        _BWD_WS[key] = v
     return v
 
 
@@ -891,7 +908,7 @@ def render_backward_raise_pending(dev=None) -> None:
 
 def render_backward(rgba_layers: torch.Tensor, homs: torch.Tensor, dout: torch.Tensor,
                     workspace: torch.Tensor | None = None, ckpt: torch.Tensor | None = None,
-                    check: bool | None = None) -> torch.Tensor:
+                    check: bool | None = None, want_dhoms: bool = False, want_dmpi: bool = True):
     """d(mpi_render_view_torch)/d(rgba_layers): rgba_layers [B,H,W,P,4] (read in place when
     its planes are contiguous per pixel, incl. a stride-0 broadcast batch; other layouts
     are made contiguous first), homs [B,P,9] (the forward's), dout [B,H,W,3] ->
@@ -901,7 +918,14 @@ def render_backward(rgba_layers: torch.Tensor, homs: torch.Tensor, dout: torch.T
     (skips recomputing the forward composite).  check (default MPIV_BWD_CHECK): read the
     fallback's abort count back and raise if any view aborted (costs a synchronisation); left at
     None without MPIV_BWD_CHECK, the count is read back asynchronously and a later call raises
-    (_AbortMonitor); False: not watched at all."""
+    (_AbortMonitor); False: not watched at all.
+    want_dhoms: also return d(render)/d(homs) [B,P,9] on the device (render_bwd_cam.hip; per-sample
+    terms bit-exact to the reference, the frame sum in a fixed order of its own): the result is then the
+    pair (grad, dhoms).  want_dmpi=False (with want_dhoms): a fixed MPI -- grad is None and the gather /
+    check / fallback half of the backward does not run.  workspace then needs
+    mpiv_render_backward_cam_workspace_size_min bytes."""
+    if not want_dmpi and not want_dhoms:
+        raise RuntimeError("render_backward: nothing to compute (want_dmpi and want_dhoms are both False)")
     dev = _dev(rgba_layers, dout)
     B, H, W, P, _ = rgba_layers.shape
     if tuple(dout.shape) != (B, H, W, 3):
@@ -910,12 +934,12 @@ def render_backward(rgba_layers: torch.Tensor, homs: torch.Tensor, dout: torch.T
     L = load()
     # a caller's workspace of at least the minimum (plane groups, render_bwd.hip); our own: the
     # one-group size (the fastest schedule) unless MPIV_BWD_MIN_WS=1
-    need, full = _bwd_ws_sizes(L, H, W, P)
+    need, full = _bwd_ws_sizes(L, H, W, P, want_dhoms)
     ws = workspace if workspace is not None else torch.empty(need if BWD_MIN_WS else full, dtype=torch.uint8,
                                                              device=dev)
     if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.device != dev:
         raise RuntimeError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on {dev}")
-    grad = torch.empty((B, H, W, P, 4), device=dev, dtype=torch.float32)
+    grad = torch.empty((B, H, W, P, 4), device=dev, dtype=torch.float32) if want_dmpi else None
     h = _up(homs.reshape(B, P, 9), dev, "homs")
     dout = dout.contiguous()
     if ckpt is not None and (tuple(ckpt.shape) != (B, (P + 7) // 8, H, W, 4) or not ckpt.is_contiguous()
@@ -929,35 +953,47 @@ def render_backward(rgba_layers: torch.Tensor, homs: torch.Tensor, dout: torch.T
         if mon is None:
             mon = _ABORTS.setdefault(key, _AbortMonitor(dev, L))
         mon.raise_completed()  # an earlier call's abort, read without waiting
-    _call("mpiv_render_backward_watched" if watch else "mpiv_render_backward", src, _strides(src), B, H, W, P, h, dout,
-          ckpt, grad, ws, ws.numel(), _stream(dev))
+    dhoms = None
+    if want_dhoms:
+        dhoms = torch.empty((B, P, 9), device=dev, dtype=torch.float32)
+        _call("mpiv_render_backward_cam", src, _strides(src), B, H, W, P, h, dout, ckpt, grad, dhoms, ws, ws.numel(),
+              1 if watch else 0, _stream(dev))
+    else:
+        _call("mpiv_render_backward_watched" if watch else "mpiv_render_backward", src, _strides(src), B, H, W, P, h,
+              dout, ckpt, grad, ws, ws.numel(), _stream(dev))
     if BWD_CHECK if check is None else check:
         n = render_backward_status(ws, H, W, P)
         if n:
             raise RuntimeError(f"mpiv_render_backward: the bucket fallback aborted on {n} of {B} views "
                                "(their gradients are NaN)")
-    return grad
+    return (grad, dhoms) if want_dhoms else grad
 
 
 class RenderFunction(torch.autograd.Function):
-    """Autograd node of the fused render: forward = render(), backward =
-    render_backward() (w.r.t. rgba_layers; homographies come from poses and
-    intrinsics, which the reference's training never differentiates)."""
+    """Autograd node of the fused render: forward = render(), backward = render_backward() w.r.t.
+    rgba_layers and, when the homographies require grad (a device tensor at the end of
+    _host.render_homographies_autograd's chain from tgt_pose, planes and intrinsics), w.r.t. them."""
 
     @staticmethod
     def forward(ctx, rgba_layers, homs):
-        ctx.homs = homs
-        if ctx.needs_input_grad[0]:  # keep the composite checkpoints for the backward
-            out, ckpt = render_train(rgba_layers, homs)
+        ctx.homs = homs.detach()
+        ctx.homs_shape = tuple(homs.shape)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:  # keep the composite checkpoints for the backward
+            # (a camera gradient reads a stride-0 broadcast MPI in place: every view has its checkpoints)
+            out, ckpt = render_train(rgba_layers, ctx.homs, broadcast_in_place=ctx.needs_input_grad[1])
             ctx.save_for_backward(rgba_layers, ckpt)
             return out
         ctx.save_for_backward(rgba_layers, None)
-        return render(rgba_layers, homs)
+        return render(rgba_layers, ctx.homs)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
         rgba_layers, ckpt = ctx.saved_tensors
+        if ctx.needs_input_grad[1]:
+            grad, dhoms = render_backward(rgba_layers, ctx.homs, dout, ckpt=ckpt, want_dhoms=True,
+                                          want_dmpi=ctx.needs_input_grad[0])
+            return grad, dhoms.reshape(ctx.homs_shape)
         grad = render_backward(rgba_layers, ctx.homs, dout, ckpt=ckpt) if ctx.needs_input_grad[0] else None
         return grad, None
 
@@ -1051,13 +1087,15 @@ class NetOutputRenderFunction(torch.autograd.Function):
     texel rows the render samples only, mpiv_assemble_mpi_sampled),
     render_backward with those checkpoints, the assembly adjoint -- the two-step chain's own
     kernels in its order, so d pred / d ref_img are bit-identical to it and to the reference's
-    autograd (tests/golden/netout_train.npz)."""
+    autograd (tests/golden/netout_train.npz).  Homographies that require grad (a device tensor, see
+    RenderFunction) get theirs from the same chain (render_bwd_cam.hip)."""
 
     @staticmethod
     def forward(ctx, mpi_pred, fg, homs, P):
         ctx.P = P
-        ctx.homs = homs
-        out, ckpt = render_net_output_train(mpi_pred, fg, P, homs)
+        ctx.homs = homs.detach()
+        ctx.homs_shape = tuple(homs.shape)
+        out, ckpt = render_net_output_train(mpi_pred, fg, P, ctx.homs)
         ctx.save_for_backward(mpi_pred, fg, ckpt)
         return out
 
@@ -1065,15 +1103,24 @@ class NetOutputRenderFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, dout):
         mpi_pred, fg, ckpt = ctx.saved_tensors
-        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+        want_mpi = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        want_cam = ctx.needs_input_grad[2]
+        if not (want_mpi or want_cam):
             return None, None, None, None
         # only the texel rows the render samples (round 6): the chain reads no other
         rgba = assemble_mpi_sampled(mpi_pred, fg, ctx.P, ctx.homs)
-        drgba = render_backward(rgba, ctx.homs, dout, ckpt=ckpt)
+        dhoms = None
+        if want_cam:
+            drgba, dhoms = render_backward(rgba, ctx.homs, dout, ckpt=ckpt, want_dhoms=True, want_dmpi=want_mpi)
+            dhoms = dhoms.reshape(ctx.homs_shape)
+        else:
+            drgba = render_backward(rgba, ctx.homs, dout, ckpt=ckpt)
         del rgba  # the re-assembled MPI lives only for the chain
+        if not want_mpi:
+            return None, None, dhoms, None
         res = assemble_mpi_backward(drgba, mpi_pred, fg, ctx.P, want_dfg=ctx.needs_input_grad[1])
         dpred, dfg = res if ctx.needs_input_grad[1] else (res, None)
-        return (dpred if ctx.needs_input_grad[0] else None), dfg, None, None
+        return (dpred if ctx.needs_input_grad[0] else None), dfg, dhoms, None
 
 
 def assemble_mpi_backward(drgba: torch.Tensor, mpi_pred: torch.Tensor, fg: torch.Tensor, P: int,

@@ -22,6 +22,7 @@
 #include "render_ring.hip"
 #include "render_mv.hip"
 #include "render_bwd.hip"
+#include "render_bwd_cam.hip"
 #include "sweep.hip"
 #include "geometry.hip"
 #include "assemble.hip"
@@ -940,10 +941,27 @@ int* mpiv_render_backward_abort_flag(int device) {
 
 constexpr int64_t kFoldCheckMaxBlocks = 8192;  // gather grids up to this size run the check in their last block
 
+// The camera gradient's outputs and scratch (mpiv_render_backward_cam; render_bwd_cam.hip): after every
+// chain launch bwd_cam_kernel reduces the group's d samples to per-tile partials, and one
+// bwd_cam_sum_kernel per view folds them into dhoms[v].  The scratch sits behind the backward's own
+// workspace: the partials [P][tiles][9], then one frame of float4 (the checkpoint forward's frame when
+// there is no d MPI to lend its storage).
+struct CamOut {
+    float* dhoms;
+    float* partials;
+    float* frame;
+    int ntiles;
+};
+
+static size_t cam_extra_bytes(int H, int W, int P) {
+    const size_t ntiles = (size_t)blocks(W, kCamTX) * blocks(H, kCamTY);
+    return align256((size_t)P * ntiles * 36) + align256((size_t)H * W * 16);
+}
+
 static int render_backward_impl(const char* nm, const float* mpi, const int64_t st[5], int V, int H, int W, int P,
                                 const float* homs, const float* dout, const float* ckpt, float* dmpi, void* workspace,
-                                size_t ws_bytes, void* stream, bool watched) {
-    if (!mpi || !st || !homs || !dout || !dmpi || !workspace) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+                                size_t ws_bytes, void* stream, bool watched, const CamOut* cam = nullptr) {
+    if (!mpi || !st || !homs || !dout || (!dmpi && !cam) || !workspace) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
     if (V <= 0 || H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
     // in place: planes contiguous per pixel (16-B texels), every tap below the buffer range
     const int64_t rec = ((int64_t)(H - 1) * st[1] + (int64_t)(W - 1) * st[2]) * 4 + kBwdCH * 16;
@@ -973,7 +991,7 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     // workspace holds two windows (the default workspace does)
     const bool fast2 = H >= 2 && W >= 2;
     const int GPo = bwd_group_planes(H, W, P);
-    const bool overlap = MPIV_AB && opt(kOptBwdOverlap) != 0 && fast2 && GPo < P && !wide &&
+    const bool overlap = MPIV_AB && opt(kOptBwdOverlap) != 0 && fast2 && GPo < P && !wide && !cam &&
                          ws_bytes >= bwd_layout(H, W, P, GPo, nullptr, nullptr, nullptr, 2);
     const int GP = overlap ? GPo : (opt(kOptBwdGroup) > 0 || ws_bytes < bwd_layout(H, W, P, P, nullptr, nullptr))
                                        ? bwd_group_planes(H, W, P) : P;
@@ -1126,6 +1144,59 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
         else
             bwd_chain_strip_kernel<8><<<nb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, ckv, wg, h_lds, c_lo, c_hi, gbuf);
     };
+    // the camera gradient of chunks [c_lo, c_hi) from the window's d samples, and a view's final sum
+    auto cam_chunks = [&](const float* mv, const float* hv, const BwdWs& wg, int c_lo, int c_hi) {
+        const dim3 nb((unsigned)cam->ntiles, (unsigned)(c_hi - c_lo));
+        if (!fast && wide)
+            bwd_cam_kernel<0, true><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
+        else if (!fast)
+            bwd_cam_kernel<0, false><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
+        else if (wide)
+            bwd_cam_kernel<1, true><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
+        else
+            bwd_cam_kernel<1, false><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
+    };
+    auto cam_sum = [&](int v) {
+        bwd_cam_sum_kernel<<<P, 256, 0, q>>>(cam->partials, cam->ntiles, cam->dhoms + (int64_t)v * P * 9);
+    };
+    if (cam && !dmpi) {
+        // Fixed MPI: the chain and the camera kernels only -- no boxes, gather, check or fallback.  The
+        // chain still counts its pairs, so the counters are zeroed before it (the folded schedule's box
+        // kernel is not launched) and again behind it: the head is left as the check kernel leaves it.
+        const size_t head = 2 * kCtrSlots * 8 + 256;
+        if (folded && hipMemsetAsync(ws.truth, 0, head, q) != hipSuccess)
+            return fail(MPIV_ERR_HIP, "%s: hipMemsetAsync failed", nm);
+        const int n = (P + kBwdCH - 1) / kBwdCH;
+        for (int v = 0; v < V; ++v) {
+            const float* hv = homs + (int64_t)v * P * 9;
+            const float* dv = dout + (int64_t)v * HW * 3;
+            const float* mv = mpi + (int64_t)v * st[0];
+            const float4* ck = ckpt ? reinterpret_cast<const float4*>(ckpt) + (int64_t)v * n * HW : nullptr;
+            if (!fast) {  // H or W < 2: the generic two-pass chain, one group
+                const unsigned cb = blocks(W, kTileX) * blocks(H, kTileY);
+                if (wide)
+                    bwd_chain_kernel<0, false, 1, true><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
+                else
+                    bwd_chain_kernel<0, false, 1><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
+                cam_chunks(mv, hv, ws, 0, n);
+            } else {
+                if (!ck) {
+                    forward_ckpt(mv, hv, cam->frame);
+                    ck = ws.ckpt;
+                }
+                for (int grp = G - 1; grp >= 0; --grp) {
+                    const int p_lo = grp * GP, p_hi = std::min(P, p_lo + GP);
+                    BwdWs wg = ws;
+                    wg.ds_p0 = p_lo;
+                    chain_strip(mv, hv, dv, ck, wg, p_lo / kBwdCH, (p_hi + kBwdCH - 1) / kBwdCH);
+                    cam_chunks(mv, hv, wg, p_lo / kBwdCH, (p_hi + kBwdCH - 1) / kBwdCH);
+                }
+            }
+            cam_sum(v);
+        }
+        if (hipMemsetAsync(ws.truth, 0, head, q) != hipSuccess) return fail(MPIV_ERR_HIP, "%s: hipMemsetAsync failed", nm);
+        return launched(nm);
+    }
     for (int v = 0; v < V; ++v) {
         const float* hv = homs + (int64_t)v * P * 9;
         const float* dv = dout + (int64_t)v * HW * 3;
@@ -1147,6 +1218,7 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
                 BwdWs wg = ws;
                 wg.ds_p0 = p_lo;  // the window holds the group's d samples: planes p_lo .. p_hi-1
                 chain_strip(mv, hv, dv, ckv, wg, p_lo / kBwdCH, (p_hi + kBwdCH - 1) / kBwdCH);
+                if (cam) cam_chunks(mv, hv, wg, p_lo / kBwdCH, (p_hi + kBwdCH - 1) / kBwdCH);
                 if (!force)
                     bwd_gather_kernel<false><<<(unsigned)(ntiles * blocks(p_hi - p_lo, kGPl)), kGThreads, 0, q>>>(
                         g, hv, wg, gv, margin, p_lo, p_hi - p_lo);
@@ -1159,6 +1231,7 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
                                                                          p_hi);
             }
             bwd_poison_kernel<<<256, 256, 0, q>>>(ws.flag, gv, (int64_t)P * HW, nullptr, nullptr, ws.sink);
+            if (cam) cam_sum(v);
             continue;
         }
         const int R = fast ? chunk_rows() : 1;
@@ -1200,6 +1273,10 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
         else if (ck) MPIV_CHAIN(true, 1);
         else MPIV_CHAIN(false, 1);
 #undef MPIV_CHAIN
+        if (cam) {  // one group: every plane's d samples are resident until the next view's chain
+            cam_chunks(mv, hv, ws, 0, (P + kBwdCH - 1) / kBwdCH);
+            cam_sum(v);
+        }
         if (folded) {
             // the check in the gather's last block costs every block a wait for its stores and a barrier at
             // its end (+2 % at config 4's 131072 blocks, profiles/r06_bwd_fold.json): small grids only, where
@@ -1274,6 +1351,41 @@ int mpiv_render_backward_watched(const float* mpi, const int64_t st[5], int V, i
     if (!abort_flags_dev()) return fail(MPIV_ERR_HIP, "mpiv_render_backward_watched: no page-locked abort flag");
     return render_backward_impl("mpiv_render_backward_watched", mpi, st, V, H, W, P, homs, dout, ckpt, dmpi, workspace,
                                 ws_bytes, stream, true);
+}
+
+int mpiv_render_backward_cam(const float* mpi, const int64_t st[5], int V, int H, int W, int P, const float* homs,
+                             const float* dout, const float* ckpt, float* dmpi, float* dhoms, void* workspace,
+                             size_t ws_bytes, int watched, void* stream) {
+    const char* nm = "mpiv_render_backward_cam";
+    if (!dhoms || !workspace) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (V <= 0 || H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if (reinterpret_cast<uintptr_t>(dhoms) & 3) return fail(MPIV_ERR_ARG, "%s: d homographies must be 4-byte aligned", nm);
+    if (view_too_large(H, W, P)) return fail(MPIV_ERR_ARG, kViewTooLarge, nm);
+    const size_t extra = cam_extra_bytes(H, W, P);
+    if (ws_bytes < extra + mpiv_render_backward_workspace_size_min(H, W, P))
+        return fail(MPIV_ERR_ARG, "%s: workspace too small (%zu < %zu bytes)", nm, ws_bytes,
+                    extra + mpiv_render_backward_workspace_size_min(H, W, P));
+    if (watched && !abort_flags_dev()) return fail(MPIV_ERR_HIP, "%s: no page-locked abort flag", nm);
+    // the backward's own workspace in front (its size picks the schedule, as in mpiv_render_backward),
+    // the camera scratch behind it
+    const size_t base = (ws_bytes - extra) & ~(size_t)255;
+    CamOut cam;
+    cam.dhoms = dhoms;
+    cam.ntiles = (int)(blocks(W, kCamTX) * blocks(H, kCamTY));
+    cam.partials = reinterpret_cast<float*>(static_cast<char*>(workspace) + base);
+    cam.frame = reinterpret_cast<float*>(static_cast<char*>(workspace) + base + align256((size_t)P * cam.ntiles * 36));
+    return render_backward_impl(nm, mpi, st, V, H, W, P, homs, dout, ckpt, dmpi, workspace, base, stream, watched != 0,
+                                &cam);
+}
+
+size_t mpiv_render_backward_cam_workspace_size(int H, int W, int P) {
+    if (H <= 0 || W <= 0 || P <= 0) return 0;
+    return align256(mpiv_render_backward_workspace_size(H, W, P)) + cam_extra_bytes(H, W, P);
+}
+
+size_t mpiv_render_backward_cam_workspace_size_min(int H, int W, int P) {
+    if (H <= 0 || W <= 0 || P <= 0) return 0;
+    return align256(mpiv_render_backward_workspace_size_min(H, W, P)) + cam_extra_bytes(H, W, P);
 }
 
 int mpiv_render_backward_status(const void* workspace, int H, int W, int P, int* aborted_views, void* stream) {

@@ -135,6 +135,13 @@ def projective_forward_homography_torch(src_images, intrinsics, pose, depths):
     return planar_transform_torch(src_images, grid, intrinsics, intrinsics, rot, t, n_hat, a)
 
 
+def _camera_grad(tgt_pose, planes, intrinsics) -> bool:
+    """True when the caller asks for a gradient w.r.t. the camera: the render then takes the
+    autograd homography chain; otherwise nothing changes."""
+    return torch.is_grad_enabled() and any(isinstance(x, torch.Tensor) and x.requires_grad
+                                           for x in (tgt_pose, planes, intrinsics))
+
+
 def mpi_render_view_torch(rgba_layers, tgt_pose, planes, intrinsics):
     """Render [B, H, W, 3] target views from an MPI [B, H, W, P, 4] (utils.py:267-294).
 
@@ -142,10 +149,17 @@ def mpi_render_view_torch(rgba_layers, tgt_pose, planes, intrinsics):
     as in the reference, utils.py:279).  The whole warp + over-composite runs as ONE
     fused HIP kernel; the MPI may be a stride-0 broadcast over the batch.  When
     rgba_layers requires grad the result is differentiable w.r.t. it (HIP backward,
-    bit-exact to the reference's autograd)."""
+    bit-exact to the reference's autograd).  When tgt_pose, planes or intrinsics requires grad it
+    is differentiable w.r.t. them too, as in the reference: d frame / d homographies in HIP
+    (render_bwd_cam.hip), the 3x3 chain behind it in torch on the host
+    (_host.render_homographies_autograd: one device-to-host copy of the pose per call)."""
     batch_size = tgt_pose.shape[0]
     n_planes = len(planes)
     depths = planes.reshape([n_planes, 1])  # AttributeError on a list, like the reference
+    if rgba_layers.is_cuda and _camera_grad(tgt_pose, planes, intrinsics):
+        homs = _host.render_homographies_autograd(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
+        # (device homographies into the Function: autograd's copy node carries their gradient back)
+        return _lib.RenderFunction.apply(rgba_layers, homs.to(rgba_layers.device))
     if tgt_pose.is_cuda and rgba_layers.is_cuda:  # poses in HBM: the chain runs there too
         homs = _host.render_homographies_device(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
     else:
@@ -247,10 +261,15 @@ def mpi_render_net_output_torch(mpi_pred, ref_img, tgt_pose, planes, intrinsics)
     w.r.t. mpi_pred and ref_img when either requires grad (_lib.NetOutputRenderFunction: the
     training forward also writes the composite checkpoints; the backward re-assembles the MPI
     for the adjoint, so the MPI is never held between forward and backward), bit-exact to the
-    reference's autograd of the two-step form."""
+    reference's autograd of the two-step form.  Differentiable w.r.t. tgt_pose, planes and
+    intrinsics too when any of them requires grad (see mpi_render_view_torch)."""
     batch_size = tgt_pose.shape[0]
     n_planes = len(planes)
     depths = planes.reshape([n_planes, 1])
+    if mpi_pred.is_cuda and _camera_grad(tgt_pose, planes, intrinsics):
+        homs = _host.render_homographies_autograd(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
+        return _lib.NetOutputRenderFunction.apply(mpi_pred, ref_img.to(mpi_pred.device), homs.to(mpi_pred.device),
+                                                  n_planes)
     if tgt_pose.is_cuda:
         homs = _host.render_homographies_device(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
     else:
