@@ -435,28 +435,135 @@ def synth_mpi_packed(seed: int, H: int, W: int, p_begin: int, p_end: int, device
     return packed
 
 
-def pack_planes_u8(view: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    """One 8-bit MPI view [H, W, P, 4] uint8 (any strides) -> packed u8 planes
-    [P, H+4, W+4] int32 (RGBA bytes of each texel, R lowest) with the zero border."""
-    if not isinstance(view, torch.Tensor) or view.dtype != torch.uint8:
-        raise RuntimeError("pack_planes_u8 expects a uint8 [H, W, P, 4] tensor")
+# ---- narrow-texel MPIs: 8-bit and half-precision RGBA (csrc/render_texel.hip) ----
+#
+# Views per launch from which a narrow MPI is rendered through its exact float copy (the float rows
+# kernel; the copy is memoised, packed_float_copy).  These are steady-state kernel times: the
+# thresholds are for a packed MPI that is rendered again and again.
+# u8: the float rows kernel at 125 views: 26.6 ms vs 29.8 for the u8 kernel, VALU-bound on the exact
+# per-tap conversion; at one view the u8 kernel reads 4x fewer bytes and wins, 0.31 vs 0.38 ms.
+U8_FLOAT_MIN_VIEWS = int(os.environ.get("MPIV_U8_FLOAT_MIN_VIEWS", "32"))
+# f16: on config 4 the f16 kernel wins up to 4 views (one view 0.265 vs 0.376 ms for the float kernel),
+# the float rows kernel from 8 (1.49 vs 1.56 ms; 125 views 20.2 vs 23.4), on config 2 from 8 too
+# (0.147 vs 0.190) (profiles/f16_render.jsonl, DESIGN.md §4 "f16 texels").  A caller that packs,
+# renders ONE launch and drops the MPI (mpi_render_view_f16) pays the copy (0.52 ms at config 4) every
+# time: copy + float kernel beat the f16 kernel only from F16_FLOAT_ONCE_MIN_VIEWS views (config 4 at
+# 32 views 5.50 + 0.52 vs 6.00 ms, a tie; at 64 views 10.46 + 0.52 vs 11.96).
+F16_FLOAT_MIN_VIEWS = int(os.environ.get("MPIV_F16_FLOAT_MIN_VIEWS", "8"))
+F16_FLOAT_ONCE_MIN_VIEWS = 64
+
+# A format: its name in the entry points (mpiv_pack_planes_<name>, mpiv_unpack_planes_<name>,
+# mpiv_render_packed_<name>[_ct]), the dtype of the caller's [H, W, P, 4] view, the packed tensor
+# ([P, H+4, W+4] + tail, of dtype packed) and the float-route threshold.
+_Tex = collections.namedtuple("_Tex", "name view packed tail float_min_views")
+_U8 = _Tex("u8", torch.uint8, torch.int32, (), U8_FLOAT_MIN_VIEWS)  # a texel: one word, RGBA bytes, R lowest
+_F16 = _Tex("f16", torch.float16, torch.float16, (4,), F16_FLOAT_MIN_VIEWS)  # a texel: 4 halves, 8 B
+
+
+def _dt(dtype: torch.dtype) -> str:
+    return str(dtype).replace("torch.", "")
+
+
+def _tex_pack(t: _Tex, view: torch.Tensor, out: torch.Tensor | None) -> torch.Tensor:
+    what = f"pack_planes_{t.name}"
+    if not isinstance(view, torch.Tensor):
+        raise TypeError(f"expected a torch.Tensor, got {type(view).__name__}")
+    if view.dtype != t.view:
+        raise RuntimeError(f"{what} expects a {_dt(t.view)} [H, W, P, 4] tensor, got {view.dtype}")
     if view.device.type != "cuda":
         raise RuntimeError("mpi_vision_amd kernels need ROCm device tensors; there is no CPU path")
     dev = view.device
     H, W, P, C = view.shape
     if C != 4:
         raise RuntimeError(f"MPI texels must have 4 channels (RGBA), got {C}")
-    shape = (P, H + 2 * PAD, W + 2 * PAD)
+    shape = (P, H + 2 * PAD, W + 2 * PAD) + t.tail
     if out is None:
-        packed = torch.empty(shape, device=dev, dtype=torch.int32)
-    elif tuple(out.shape) != shape or out.dtype != torch.int32 or not out.is_contiguous() or out.device != dev:
-        raise RuntimeError(f"pack_planes_u8: out must be a contiguous int32 {shape} tensor on {dev}")
+        packed = torch.empty(shape, device=dev, dtype=t.packed)
+    elif tuple(out.shape) != shape or out.dtype != t.packed or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"{what}: out must be a contiguous {_dt(t.packed)} {shape} tensor on {dev}")
     else:
         packed = out
-    _call("mpiv_pack_planes_u8", view, _strides(view), H, W, P, packed, _stream(dev))
+    _call(f"mpiv_{what}", view, _strides(view), H, W, P, packed, _stream(dev))
     if out is not None:
         _wrote(packed)
     return packed
+
+
+def _tex_hw(t: _Tex, packed: torch.Tensor):
+    """(P, H, W) of a packed narrow MPI, after checking that it is one."""
+    if not isinstance(packed, torch.Tensor):
+        raise TypeError(f"expected a torch.Tensor, got {type(packed).__name__}")
+    if (packed.dtype != t.packed or packed.dim() != 3 + len(t.tail) or tuple(packed.shape[3:]) != t.tail
+            or not packed.is_contiguous()):
+        layout = ", ".join(("P", "H+4", "W+4") + tuple(map(str, t.tail)))
+        raise RuntimeError(f"packed {t.name} MPI must be a contiguous {_dt(t.packed)} [{layout}] tensor, got "
+                           f"{packed.dtype} {tuple(packed.shape)}")
+    if packed.device.type != "cuda":
+        raise RuntimeError("mpi_vision_amd kernels need ROCm device tensors; there is no CPU path")
+    return packed.shape[0], packed.shape[1] - 2 * PAD, packed.shape[2] - 2 * PAD
+
+
+def _tex_unpack(t: _Tex, packed: torch.Tensor) -> torch.Tensor:
+    P, H, W = _tex_hw(t, packed)
+    out = torch.empty(packed_shape(H, W, P), device=packed.device, dtype=torch.float32)
+    _call(f"mpiv_unpack_planes_{t.name}", packed, H, W, P, out, _stream(packed.device))
+    return out
+
+
+def _render_views(what: str, packed: torch.Tensor, phw, homs: torch.Tensor, out: torch.Tensor | None):
+    """mpiv_<what>: a packed MPI of any format + homs [V,P,9] (host or device) -> [V,H,W,3]."""
+    P, H, W = phw
+    dev = packed.device
+    V = homs.shape[0]
+    h = _up(homs.reshape(V, P, 9), dev, "homs")
+    if out is None:
+        out = torch.empty((V, H, W, 3), device=dev, dtype=torch.float32)
+    else:
+        _check_out(out, (V, H, W, 3), dev, what)
+    if V == 0:
+        return out
+    _call(f"mpiv_{what}", packed, H, W, P, h, V, out, _stream(dev))
+    return out
+
+
+def _render_views_ct(what: str, packed: torch.Tensor, phw, homs: torch.Tensor, back: bool, p_begin: int,
+                     p_end: int | None, out: torch.Tensor | None):
+    """mpiv_<what>: the plane-range partial (C, T) [V,H,W,4] of a packed MPI of any format."""
+    P, H, W = phw
+    dev = packed.device
+    p_end = P if p_end is None else p_end
+    V = homs.shape[0]
+    h = _up(homs.reshape(V, P, 9), dev, "homs")
+    if out is None:
+        out = torch.empty((V, H, W, 4), device=dev, dtype=torch.float32)
+    else:
+        _check_out(out, (V, H, W, 4), dev, what)
+    _call(f"mpiv_{what}", packed, H, W, P, p_begin, p_end, int(back), h, V, out, _stream(dev))
+    return out
+
+
+def _tex_render(t: _Tex, packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None,
+                route_float: bool | None) -> torch.Tensor:
+    phw = _tex_hw(t, packed)
+    if route_float is None:
+        route_float = homs.shape[0] >= t.float_min_views
+    if route_float:
+        if homs.device.type == "cpu":
+            host_under_capture("homs")  # (before the float copy is launched)
+        return render_packed(packed_float_copy(packed), homs, out=out)
+    return _render_views(f"render_packed_{t.name}", packed, phw, homs, out)
+
+
+def pack_planes_u8(view: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One 8-bit MPI view [H, W, P, 4] uint8 (any strides) -> packed u8 planes
+    [P, H+4, W+4] int32 (RGBA bytes of each texel, R lowest) with the zero border."""
+    return _tex_pack(_U8, view, out)
+
+
+def pack_planes_f16(view: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """One half-precision MPI view [H, W, P, 4] float16 (any strides) -> packed f16 planes
+    [P, H+4, W+4, 4] float16 (8-B texels) with the zero border."""
+    return _tex_pack(_F16, view, out)
 
 
 def synth_mpi_packed_u8(seed: int, H: int, W: int, p_begin: int, p_end: int, device) -> torch.Tensor:
@@ -469,23 +576,23 @@ def synth_mpi_packed_u8(seed: int, H: int, W: int, p_begin: int, p_end: int, dev
 
 
 def _u8_hw(packed: torch.Tensor):
-    if packed.dim() != 3 or packed.dtype != torch.int32 or not packed.is_contiguous() or packed.device.type != "cuda":
-        raise RuntimeError("packed u8 MPI must be a contiguous int32 [P, H+4, W+4] ROCm tensor")
-    return packed.shape[0], packed.shape[1] - 2 * PAD, packed.shape[2] - 2 * PAD
+    return _tex_hw(_U8, packed)
+
+
+def _f16_hw(packed: torch.Tensor):
+    return _tex_hw(_F16, packed)
 
 
 def unpack_planes_u8(packed: torch.Tensor) -> torch.Tensor:
     """packed u8 [P,H+4,W+4] -> the packed float MPI [P,H+4,W+4,4] of u8.float() / 255 (exact)."""
-    P, H, W = _u8_hw(packed)
-    out = torch.empty(packed_shape(H, W, P), device=packed.device, dtype=torch.float32)
-    _call("mpiv_unpack_planes_u8", packed, H, W, P, out, _stream(packed.device))
-    return out
+    return _tex_unpack(_U8, packed)
 
 
-# Views per launch from which render_packed_u8 renders an 8-bit MPI through its float copy (the
-# float rows kernel at 125 views: 26.6 ms vs 29.8 for the u8 kernel, VALU-bound on the exact
-# per-tap conversion; at one view the u8 kernel reads 4x fewer bytes and wins, 0.31 vs 0.38 ms).
-U8_FLOAT_MIN_VIEWS = int(os.environ.get("MPIV_U8_FLOAT_MIN_VIEWS", "32"))
+def unpack_planes_f16(packed: torch.Tensor) -> torch.Tensor:
+    """packed f16 [P,H+4,W+4,4] -> the packed float MPI [P,H+4,W+4,4] of mpi.float() (exact)."""
+    return _tex_unpack(_F16, packed)
+
+
 _U8_FLOAT: dict = {}  # device -> (key, weak reference to the u8 / f16 MPI, its float copy)
 
 
@@ -504,18 +611,19 @@ def packed_float_copy(packed: torch.Tensor) -> torch.Tensor:
     (2.2 GB at config 4); it is dropped when its MPI is freed, or by clear_float_copies().  Under a
     HIP-graph capture the memo is neither read nor written: the conversion is captured."""
     dev = packed.device
+    unpack = unpack_planes_f16 if packed.dtype == torch.float16 else unpack_planes_u8
     if torch.cuda.is_current_stream_capturing():
         # HIP-graph capture: the conversion is part of the graph, into a fresh tensor of the graph's own
         # pool -- the packed MPI is a static input whose contents change between replays, so a memo hit
         # must not skip it, and the memo's copy (freed by the next MPI) must not be captured
-        return unpack_planes_f16(packed) if packed.dtype == torch.float16 else unpack_planes_u8(packed)
+        return unpack(packed)
     key = (id(packed), packed.data_ptr(), packed._version, tuple(packed.shape),
            torch.cuda.current_stream(dev).cuda_stream)
     ent = _U8_FLOAT.get(dev)
     if ent is not None and ent[0] == key and ent[1]() is packed:
         return ent[2]
     _U8_FLOAT.pop(dev, None)  # free the old copy first
-    f = unpack_planes_f16(packed) if packed.dtype == torch.float16 else unpack_planes_u8(packed)
+    f = unpack(packed)
     _U8_FLOAT[dev] = (key, weakref.ref(packed), f)
     weakref.finalize(packed, _drop_u8_float, dev, key)
     return f
@@ -553,143 +661,32 @@ clear_u8_float_copies = clear_float_copies
 def render_packed_u8(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None = None,
                      route_float: bool | None = None) -> torch.Tensor:
     """packed u8 [P,H+4,W+4] + homs [V,P,9] -> [V,H,W,3] fp32, bit-identical to rendering the
-    float MPI u8.float() / 255 (render_u8.hip).  Launches of >= U8_FLOAT_MIN_VIEWS views
+    float MPI u8.float() / 255 (render_texel.hip).  Launches of >= U8_FLOAT_MIN_VIEWS views
     (route_float None) render the MPI's exact float copy (u8_float_copy, converted once per MPI)
     with the float kernel instead: the same bits, faster where the texture path binds."""
-    P, H, W = _u8_hw(packed)
-    if route_float is None:
-        route_float = homs.shape[0] >= U8_FLOAT_MIN_VIEWS
-    if route_float:
-        if homs.device.type == "cpu":
-            host_under_capture("homs")  # (before the float copy is launched)
-        return render_packed(u8_float_copy(packed), homs, out=out)
-    dev = packed.device
-    V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev, "homs")
-    if out is None:
-        out = torch.empty((V, H, W, 3), device=dev, dtype=torch.float32)
-    else:
-        _check_out(out, (V, H, W, 3), dev, "render_packed_u8")
-    if V == 0:
-        return out
-    _call("mpiv_render_packed_u8", packed, H, W, P, h, V, out, _stream(dev))
-    return out
+    return _tex_render(_U8, packed, homs, out, route_float)
 
 
 def render_packed_u8_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_begin: int = 0,
                         p_end: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """Plane-range partial (C, T) [V,H,W,4] of a packed u8 MPI (plane sharding)."""
-    P, H, W = _u8_hw(packed)
-    dev = packed.device
-    p_end = P if p_end is None else p_end
-    V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev, "homs")
-    if out is None:
-        out = torch.empty((V, H, W, 4), device=dev, dtype=torch.float32)
-    else:
-        _check_out(out, (V, H, W, 4), dev, "render_packed_u8_ct")
-    _call("mpiv_render_packed_u8_ct", packed, H, W, P, p_begin, p_end, int(back), h, V, out, _stream(dev))
-    return out
-
-
-def pack_planes_f16(view: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    """One half-precision MPI view [H, W, P, 4] float16 (any strides) -> packed f16 planes
-    [P, H+4, W+4, 4] float16 (8-B texels) with the zero border."""
-    if not isinstance(view, torch.Tensor):
-        raise TypeError(f"expected a torch.Tensor, got {type(view).__name__}")
-    if view.dtype != torch.float16:
-        raise RuntimeError(f"pack_planes_f16 expects a float16 [H, W, P, 4] tensor, got {view.dtype}")
-    if view.device.type != "cuda":
-        raise RuntimeError("mpi_vision_amd kernels need ROCm device tensors; there is no CPU path")
-    dev = view.device
-    H, W, P, C = view.shape
-    if C != 4:
-        raise RuntimeError(f"MPI texels must have 4 channels (RGBA), got {C}")
-    shape = packed_shape(H, W, P)
-    if out is None:
-        packed = torch.empty(shape, device=dev, dtype=torch.float16)
-    elif tuple(out.shape) != shape or out.dtype != torch.float16 or not out.is_contiguous() or out.device != dev:
-        raise RuntimeError(f"pack_planes_f16: out must be a contiguous float16 {shape} tensor on {dev}")
-    else:
-        packed = out
-    _call("mpiv_pack_planes_f16", view, _strides(view), H, W, P, packed, _stream(dev))
-    if out is not None:
-        _wrote(packed)
-    return packed
-
-
-def _f16_hw(packed: torch.Tensor):
-    if not isinstance(packed, torch.Tensor):
-        raise TypeError(f"expected a torch.Tensor, got {type(packed).__name__}")
-    if packed.dtype != torch.float16 or packed.dim() != 4 or packed.shape[-1] != 4 or not packed.is_contiguous():
-        raise RuntimeError(f"packed f16 MPI must be a contiguous float16 [P, H+4, W+4, 4] tensor, got {packed.dtype} "
-                           f"{tuple(packed.shape)}")
-    if packed.device.type != "cuda":
-        raise RuntimeError("mpi_vision_amd kernels need ROCm device tensors; there is no CPU path")
-    return packed.shape[0], packed.shape[1] - 2 * PAD, packed.shape[2] - 2 * PAD
-
-
-def unpack_planes_f16(packed: torch.Tensor) -> torch.Tensor:
-    """packed f16 [P,H+4,W+4,4] -> the packed float MPI [P,H+4,W+4,4] of mpi.float() (exact)."""
-    P, H, W = _f16_hw(packed)
-    out = torch.empty(packed_shape(H, W, P), device=packed.device, dtype=torch.float32)
-    _call("mpiv_unpack_planes_f16", packed, H, W, P, out, _stream(packed.device))
-    return out
-
-
-# Views per launch from which render_packed_f16 renders a half MPI through its float copy: on config 4
-# the f16 kernel wins up to 4 views (one view 0.265 vs 0.376 ms for the float kernel), the float rows
-# kernel from 8 (1.49 vs 1.56 ms; 125 views 20.2 vs 23.4), on config 2 from 8 too (0.147 vs 0.190)
-# (profiles/f16_render.jsonl, DESIGN.md §4 "f16 texels").  These are steady-state kernel times: the
-# threshold is for a packed MPI that is rendered again and again (the copy, 0.52 ms at config 4, is
-# memoised).  A caller that packs, renders ONE launch and drops the MPI (mpi_render_view_f16) pays the
-# copy every time: copy + float kernel beat the f16 kernel only from F16_FLOAT_ONCE_MIN_VIEWS views
-# (config 4 at 32 views 5.50 + 0.52 vs 6.00 ms, a tie; at 64 views 10.46 + 0.52 vs 11.96).
-F16_FLOAT_MIN_VIEWS = int(os.environ.get("MPIV_F16_FLOAT_MIN_VIEWS", "8"))
-F16_FLOAT_ONCE_MIN_VIEWS = 64
+    return _render_views_ct("render_packed_u8_ct", packed, _u8_hw(packed), homs, back, p_begin, p_end, out)
 
 
 def render_packed_f16(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None = None,
                       route_float: bool | None = None) -> torch.Tensor:
     """packed f16 [P,H+4,W+4,4] + homs [V,P,9] -> [V,H,W,3] fp32, bit-identical to rendering the
-    float MPI mpi.float() (render_f16.hip: half the texel bytes of the float render).  Launches of
+    float MPI mpi.float() (render_texel.hip: half the texel bytes of the float render).  Launches of
     >= F16_FLOAT_MIN_VIEWS views (route_float None) render the MPI's exact float copy
     (f16_float_copy, converted once per MPI) with the float kernel instead: the same bits, faster
     where the texture path binds (it costs the float copy's memory, 2x the f16 MPI)."""
-    P, H, W = _f16_hw(packed)
-    if route_float is None:
-        route_float = homs.shape[0] >= F16_FLOAT_MIN_VIEWS
-    if route_float:
-        if homs.device.type == "cpu":
-            host_under_capture("homs")  # (before the float copy is launched)
-        return render_packed(f16_float_copy(packed), homs, out=out)
-    dev = packed.device
-    V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev, "homs")
-    if out is None:
-        out = torch.empty((V, H, W, 3), device=dev, dtype=torch.float32)
-    else:
-        _check_out(out, (V, H, W, 3), dev, "render_packed_f16")
-    if V == 0:
-        return out
-    _call("mpiv_render_packed_f16", packed, H, W, P, h, V, out, _stream(dev))
-    return out
+    return _tex_render(_F16, packed, homs, out, route_float)
 
 
 def render_packed_f16_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_begin: int = 0,
                          p_end: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """Plane-range partial (C, T) [V,H,W,4] of a packed f16 MPI (plane sharding)."""
-    P, H, W = _f16_hw(packed)
-    dev = packed.device
-    p_end = P if p_end is None else p_end
-    V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev, "homs")
-    if out is None:
-        out = torch.empty((V, H, W, 4), device=dev, dtype=torch.float32)
-    else:
-        _check_out(out, (V, H, W, 4), dev, "render_packed_f16_ct")
-    _call("mpiv_render_packed_f16_ct", packed, H, W, P, p_begin, p_end, int(back), h, V, out, _stream(dev))
-    return out
+    return _render_views_ct("render_packed_f16_ct", packed, _f16_hw(packed), homs, back, p_begin, p_end, out)
 
 
 def unpack_planes(packed: torch.Tensor) -> torch.Tensor:
@@ -700,35 +697,15 @@ def unpack_planes(packed: torch.Tensor) -> torch.Tensor:
 
 def render_packed(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """packed [P,H+4,W+4,4] + homs [V,P,9] (host or device) -> [V,H,W,3]."""
-    dev = _dev(packed)
-    P, H, W = packed_hw(packed)
-    V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev, "homs")
-    if out is None:
-        out = torch.empty((V, H, W, 3), device=dev, dtype=torch.float32)
-    else:
-        _check_out(out, (V, H, W, 3), dev, "render_packed")
-    if V == 0:
-        return out
-    _call("mpiv_render_packed", packed, H, W, P, h, V, out, _stream(dev))
-    return out
+    _dev(packed)
+    return _render_views("render_packed", packed, packed_hw(packed), homs, out)
 
 
 def render_packed_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_begin: int = 0,
                      p_end: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """Plane-range partial (C, T) [V,H,W,4] for plane sharding."""
-    dev = _dev(packed)
-    P, H, W = packed_hw(packed)
-    p_end = P if p_end is None else p_end
-    V = homs.shape[0]
-    h = _up(homs.reshape(V, P, 9), dev, "homs")
-    if out is None:
-        out = torch.empty((V, H, W, 4), device=dev, dtype=torch.float32)
-    else:
-        _check_out(out, (V, H, W, 4), dev, "render_packed_ct")
-    _call("mpiv_render_packed_ct", packed, H, W, P, p_begin, p_end, int(back), h, V, out,
-          _stream(dev))
-    return out
+    _dev(packed)
+    return _render_views_ct("render_packed_ct", packed, packed_hw(packed), homs, back, p_begin, p_end, out)
 
 
 def render_packed_ct_rows(packed: torch.Tensor, homs: torch.Tensor, back: bool, y_begin: int, y_end: int,

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <mutex>
+#include <type_traits>
 
 #include "../../include/mpiv.h"
 
@@ -27,8 +28,7 @@
 #include "geometry.hip"
 #include "assemble.hip"
 #include "synth.hip"
-#include "render_u8.hip"
-#include "render_f16.hip"
+#include "render_texel.hip"
 
 namespace {
 
@@ -421,8 +421,8 @@ int mpiv_pack_planes(const float* mpi, const int64_t st[4], int H, int W, int P,
     if (blocks(P, kPackPl) > kMaxGridYZ) return fail(MPIV_ERR_ARG, "mpiv_pack_planes: too many planes");
     const NativeStrides s{0, st[0], st[1], st[2], st[3]};
     dim3 grid(blocks(npix, kPackPix), blocks(P, kPackPl), 1);
-    pack_planes_kernel<<<grid, 256, 0, S(stream)>>>(mpi, s, H, W, P, make_fastdiv((unsigned)(W + 2 * kPad)),
-                                                    reinterpret_cast<float4*>(packed), npix);
+    pack_planes_kernel<TexF32><<<grid, 256, 0, S(stream)>>>(mpi, s, H, W, P, make_fastdiv((unsigned)(W + 2 * kPad)),
+                                                            reinterpret_cast<float4*>(packed), npix);
     return launched("mpiv_pack_planes");
 }
 
@@ -2101,35 +2101,6 @@ int mpiv_synth_mpi_packed(uint32_t seed, int H, int W, int p_begin, int p_end, f
     return launched(nm);
 }
 
-// ---- 8-bit RGBA MPI (render_u8.hip) -------------------------------------------------
-
-int mpiv_pack_planes_u8(const uint8_t* mpi, const int64_t st[4], int H, int W, int P, uint32_t* packed,
-                        void* stream) {
-    const char* nm = "mpiv_pack_planes_u8";
-    if (!mpi || !st || !packed) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
-    if (H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
-    if (reinterpret_cast<uintptr_t>(packed) & 3) return fail(MPIV_ERR_ARG, "%s: packed must be 4-byte aligned", nm);
-    const int64_t npix = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
-    if (npix * 4 >= (int64_t)kOOB || blocks(P, kPackPl) > kMaxGridYZ)
-        return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or too many planes", nm);
-    const NativeStrides s{0, st[0], st[1], st[2], st[3]};
-    pack_planes_u8_kernel<<<dim3(blocks(npix, kPackPix), blocks(P, kPackPl)), 256, 0, S(stream)>>>(
-        mpi, s, H, W, P, make_fastdiv((unsigned)(W + 2 * kPad)), packed, npix);
-    return launched(nm);
-}
-
-int mpiv_unpack_planes_u8(const uint32_t* packed, int H, int W, int P, float* out, void* stream) {
-    const char* nm = "mpiv_unpack_planes_u8";
-    if (!packed || !out) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
-    if (H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
-    if ((reinterpret_cast<uintptr_t>(packed) & 3) || !aligned16(out))
-        return fail(MPIV_ERR_ARG, "%s: alignment (packed 4 B, out 16 B)", nm);
-    const int64_t n = (int64_t)P * (H + 2 * kPad) * (W + 2 * kPad);
-    const int64_t nb = std::min<int64_t>(blocks(n, 256), 1 << 20);
-    unpack_u8_planes_kernel<<<(unsigned)nb, 256, 0, S(stream)>>>(packed, reinterpret_cast<float4*>(out), n);
-    return launched(nm);
-}
-
 int mpiv_synth_mpi_packed_u8(uint32_t seed, int H, int W, int p_begin, int p_end, uint32_t* packed, void* stream) {
     const char* nm = "mpiv_synth_mpi_packed_u8";
     if (!packed) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
@@ -2143,179 +2114,173 @@ int mpiv_synth_mpi_packed_u8(uint32_t seed, int H, int W, int p_begin, int p_end
     return launched(nm);
 }
 
-static int render_u8_impl(const uint32_t* packed, int H, int W, int P, int p_begin, int p_end, int back,
-                          const float* homs, int V, float* out, bool ct, void* stream) {
-    const char* nm = ct ? "mpiv_render_packed_u8_ct" : "mpiv_render_packed_u8";
+// ---- narrow-texel RGBA MPIs (render_texel.hip): 8-bit (TexU8) and half-precision (TexF16) ----
+// One implementation per entry-point family, instantiated per format T.  A format's packed MPI must
+// be aligned to its texel (T::kBytes) and a padded plane must stay below 2 GiB in its own bytes.
+
+extern "C++" {  // (templates cannot have C linkage)
+
+template <class T>
+static bool tex_misaligned(const void* packed) { return reinterpret_cast<uintptr_t>(packed) & (T::kBytes - 1); }
+
+// misaligned: the format's own message for a misaligned `packed` (they differ in wording)
+template <class T>
+static int pack_planes_tex(const char* nm, const char* misaligned, const typename T::Scalar* mpi, const int64_t st[4],
+                           int H, int W, int P, void* packed, void* stream) {
+    if (!mpi || !st || !packed) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if (tex_misaligned<T>(packed)) return fail(MPIV_ERR_ARG, misaligned, nm);
+    const int64_t npix = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
+    if (npix * T::kBytes >= (int64_t)kOOB || blocks(P, kPackPl) > kMaxGridYZ)
+        return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or too many planes", nm);
+    const NativeStrides s{0, st[0], st[1], st[2], st[3]};
+    pack_planes_kernel<T><<<dim3(blocks(npix, kPackPix), blocks(P, kPackPl)), 256, 0, S(stream)>>>(
+        mpi, s, H, W, P, make_fastdiv((unsigned)(W + 2 * kPad)), static_cast<typename T::Texel*>(packed), npix);
+    return launched(nm);
+}
+
+template <class T>
+static int unpack_planes_tex(const char* nm, const void* packed, int H, int W, int P, float* out, void* stream) {
+    if (!packed || !out) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if (tex_misaligned<T>(packed) || !aligned16(out))
+        return fail(MPIV_ERR_ARG, "%s: alignment (packed %d B, out 16 B)", nm, (int)T::kBytes);
+    const int64_t n = (int64_t)P * (H + 2 * kPad) * (W + 2 * kPad);
+    const int64_t nb = std::min<int64_t>(blocks(n, 256), 1 << 20);
+    unpack_planes_kernel<T><<<(unsigned)nb, 256, 0, S(stream)>>>(static_cast<const typename T::Texel*>(packed),
+                                                                 reinterpret_cast<float4*>(out), n);
+    return launched(nm);
+}
+
+// One launch of render_u8_kernel / render_f16_kernel<CT, R, VS, D> (ct picks CT; a full composite
+// replaces the first plane whatever `back` says)
+template <class T, int R, bool VS, int D>
+static void launch_render_tex(bool ct, int64_t nb, hipStream_t q, const typename T::Texel* pk, int64_t npix,
+                              const RenderGeom& g, const TexGeom& tg, int V, int p_begin, int p_end, int back,
+                              const float* homs, float* out, int csp, int ord) {
+#define MPIV_TEX(KERNEL)                                                                                            \
+    if (ct) KERNEL<true, R, VS, D><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, tg, V, p_begin, p_end, back, homs, out, \
+                                                                csp, ord);                                           \
+    else KERNEL<false, R, VS, D><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, tg, V, p_begin, p_end, 1, homs, out, csp, \
+                                                              ord)
+    if constexpr (std::is_same<T, TexU8>::value) {
+        MPIV_TEX(render_u8_kernel);
+    } else {
+        MPIV_TEX(render_f16_kernel);
+    }
+#undef MPIV_TEX
+}
+
+template <class T>
+static int render_tex_impl(const void* packed, int H, int W, int P, int p_begin, int p_end, int back,
+                           const float* homs, int V, float* out, bool ct, void* stream) {
+    constexpr bool u8 = std::is_same<T, TexU8>::value;
+    const char* nm = u8 ? (ct ? "mpiv_render_packed_u8_ct" : "mpiv_render_packed_u8")
+                        : (ct ? "mpiv_render_packed_f16_ct" : "mpiv_render_packed_f16");
     if (!packed || !homs || !out) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
     if (V <= 0 || H < 2 || W < 2 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape (H, W >= 2)", nm);
     if (p_begin < 0 || p_end > P || p_begin >= p_end) return fail(MPIV_ERR_ARG, "%s: bad plane range", nm);
-    if ((reinterpret_cast<uintptr_t>(packed) & 3) || (ct && !aligned16(out)))
-        return fail(MPIV_ERR_ARG, "%s: alignment (packed 4 B, ct 16 B)", nm);
+    if (tex_misaligned<T>(packed) || (ct && !aligned16(out)))
+        return fail(MPIV_ERR_ARG, "%s: alignment (packed %d B, ct 16 B)", nm, (int)T::kBytes);
     const int64_t npix = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
-    if (npix * 4 >= (int64_t)kOOB || H >= (1 << 22) || W >= (1 << 22))
+    if (npix * T::kBytes >= (int64_t)kOOB || H >= (1 << 22) || W >= (1 << 22))
         return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or a side >= 2^22", nm);
     const RenderGeom g = make_geom(H, W, P);
-    U8Geom ug;
-    ug.row = g.Wp * 4;
-    ug.org = (kPad * g.Wp + kPad) * 4;
-    ug.plane_bytes = (int)(npix * 4);
-    // automatic: 4 rows per work-item with vertical tap reuse (the north taps' u8 -> float
-    // conversions are reused too): 8 views 1.93 vs 2.17 ms, 125 views 30.0 vs 33.2 ms, single
+    TexGeom tg;
+    tg.row = g.Wp * T::kBytes;
+    tg.org = (kPad * g.Wp + kPad) * T::kBytes;
+    tg.plane_bytes = (int)(npix * T::kBytes);
+    // automatic: 4 rows per work-item with vertical tap reuse (the north taps' conversions to float
+    // are reused too).  u8: 8 views 1.93 vs 2.17 ms, 125 views 30.0 vs 33.2 ms, single
     // view 0.337 vs 0.340, config-5 shard 0.611 vs 0.620 for 2 plain rows (profiles/r02_u8_render.jsonl).
-    // A/B: render_tile=2|8 plain rows; render_tile=4|8 with render_vshare=1: reuse, that many rows
     // Stretched MPIs (swapped x/(H-1) normalisation) take it only when the launch fills the chip
     // (>= 2048 tiles of 64x32, as the float route): config 2 at one view 0.080-0.089 vs 0.065 ms
     // for 2 plain rows, at 64 views 2.35 vs 2.40-2.49.
     const float sxr = (float)W / (float)(H - 1), syr = (float)H / (float)(W - 1);
     const bool square = sxr >= 0.8f && sxr <= 1.25f && syr >= 0.8f && syr <= 1.25f;
     const bool big = (int64_t)blocks(W, kTileX) * blocks(H, 4 * 8) * V >= 2048;
-    const int rt = opt(kOptRenderTile), vso = opt(kOptRenderVshare);
+    // The debug options pick u8 variants only (the f16 render ignores them).
     // render_tile: 0 automatic, -1 / 2 two plain rows, 8 eight plain rows, 4 | 8 with render_vshare=1
+    // (reuse, that many rows); u8_flight: rows in flight with reuse
+    const int rt = u8 ? opt(kOptRenderTile) : 0, vso = u8 ? opt(kOptRenderVshare) : 0, fo = u8 ? opt(kOptU8Flight) : 0;
     if (!(rt == 0 || rt == -1 || rt == 2 || rt == 8 || (rt == 4 && vso == 1)))
         return fail(MPIV_ERR_ARG, "%s: render_tile=%d (render_vshare=%d) is not a u8 render variant", nm, rt, vso);
     const bool vs = (rt == 0 && vso != -1 && (square || big)) || (vso == 1 && (rt == 4 || rt == 8));
     const int R = rt == 0 ? (vs ? 4 : 2) : vs ? rt : rt == 8 ? 8 : 2;
     const int64_t nb = (int64_t)blocks(W, kTileX) * blocks(H, 4 * R) * V;
     if (nb > kMaxGridX) return fail(MPIV_ERR_ARG, "%s: too many blocks", nm);
-    if (g_route) {  // every template argument, as rocprof's demangled name shows it
-        const int f = opt(kOptU8Flight) ? opt(kOptU8Flight) : (nb < 2048 ? 4 : 2);
-        const int d = (vs && R == 4 && (f == 4 || f == 8)) ? f : 2;
-        return note_route(nb, 256, "render_u8_kernel<%s, %d, %s, %d>", ct ? "true" : "false", R, vs ? "true" : "false", d);
-    }
-    const unsigned* pk = reinterpret_cast<const unsigned*>(packed);
-    hipStream_t q = S(stream);
+    // 4 rows in flight when the launch leaves the SIMDs few waves (one view: 1024 blocks = 4 waves
+    // per SIMD; u8 0.32 vs 0.37 ms), 2 for large launches (125 views: 30.2 vs 30.5 ms; r04j_strips_ab.jsonl)
+    const int f = fo ? fo : (nb < 2048 ? 4 : 2);
+    const int d = (vs && R == 4 && (f == 4 || f == 8)) ? f : 2;
+    if (g_route)  // every template argument, as rocprof's demangled name shows it
+        return note_route(nb, 256, "render_%s_kernel<%s, %d, %s, %d>", u8 ? "u8" : "f16", ct ? "true" : "false", R,
+                          vs ? "true" : "false", d);
     const int csp = opt(kOptRenderColsep);  // the column-separable issue path (render.hip ColSet)
     const int ord = render_tile_order(V);
-#define MPIV_U8(CT, RR, VV)                                                                                       \
-    render_u8_kernel<CT, RR, VV><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, CT ? back : 1, \
-                                                              homs, out, csp, ord)
-#if MPIV_AB  // 8 rows per work-item (A/B)
-    if (R == 8) {
-        if (vs && ct) MPIV_U8(true, 8, true);
-        else if (vs) MPIV_U8(false, 8, true);
-        else if (ct) MPIV_U8(true, 8, false);
-        else MPIV_U8(false, 8, false);
-        return launched(nm);
-    }
+#define MPIV_TEX(RR, VV, DD)                                                                                        \
+    launch_render_tex<T, RR, VV, DD>(ct, nb, S(stream), static_cast<const typename T::Texel*>(packed), npix, g, tg, \
+                                     V, p_begin, p_end, back, homs, out, csp, ord)
+    if constexpr (u8) {  // the variants only the 8-bit format has
+#if MPIV_AB
+        if (R == 8) {  // 8 rows per work-item (A/B)
+            if (vs) MPIV_TEX(8, true, 2);
+            else MPIV_TEX(8, false, 2);
+            return launched(nm);
+        }
 #endif
-    // 4 rows in flight when the launch leaves the SIMDs few waves (one view: 1024 blocks = 4 waves
-    // per SIMD; 0.32 vs 0.37 ms), 2 for large launches (125 views: 30.2 vs 30.5 ms; r04j_strips_ab.jsonl)
-    const int u8f = opt(kOptU8Flight) ? opt(kOptU8Flight) : (nb < 2048 ? 4 : 2);
-    if (vs && u8f == 8) {  // 8 rows in flight (two planes' rows)
-        if (ct) render_u8_kernel<true, 4, true, 8><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, back,
-                                                                              homs, out, csp, ord);
-        else render_u8_kernel<false, 4, true, 8><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, 1,
-                                                                             homs, out, csp, ord);
-    } else if (vs && u8f == 4) {  // 4 rows in flight
-        if (ct) render_u8_kernel<true, 4, true, 4><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, back,
-                                                                              homs, out, csp, ord);
-        else render_u8_kernel<false, 4, true, 4><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, ug, V, p_begin, p_end, 1,
-                                                                             homs, out, csp, ord);
-    } else if (vs) {
-        if (ct) MPIV_U8(true, 4, true);
-        else MPIV_U8(false, 4, true);
-    } else if (ct) MPIV_U8(true, 2, false);
-    else MPIV_U8(false, 2, false);
-#undef MPIV_U8
+        if (d == 8) {  // 8 rows in flight (two planes' rows)
+            MPIV_TEX(4, true, 8);
+            return launched(nm);
+        }
+    }
+    if (d == 4) MPIV_TEX(4, true, 4);
+    else if (vs) MPIV_TEX(4, true, 2);
+    else MPIV_TEX(2, false, 2);
+#undef MPIV_TEX
     return launched(nm);
+}
+
+}  // extern "C++"
+
+int mpiv_pack_planes_u8(const uint8_t* mpi, const int64_t st[4], int H, int W, int P, uint32_t* packed,
+                        void* stream) {
+    return pack_planes_tex<TexU8>("mpiv_pack_planes_u8", "%s: packed must be 4-byte aligned", mpi, st, H, W, P, packed,
+                                  stream);
+}
+
+int mpiv_pack_planes_f16(const uint16_t* mpi, const int64_t st[4], int H, int W, int P, uint16_t* packed,
+                         void* stream) {
+    return pack_planes_tex<TexF16>("mpiv_pack_planes_f16", "%s: alignment (packed 8 B)", mpi, st, H, W, P, packed,
+                                   stream);
+}
+
+int mpiv_unpack_planes_u8(const uint32_t* packed, int H, int W, int P, float* out, void* stream) {
+    return unpack_planes_tex<TexU8>("mpiv_unpack_planes_u8", packed, H, W, P, out, stream);
+}
+
+int mpiv_unpack_planes_f16(const uint16_t* packed, int H, int W, int P, float* out, void* stream) {
+    return unpack_planes_tex<TexF16>("mpiv_unpack_planes_f16", packed, H, W, P, out, stream);
 }
 
 int mpiv_render_packed_u8(const uint32_t* packed, int H, int W, int P, const float* homs, int V, float* out,
                           void* stream) {
-    return render_u8_impl(packed, H, W, P, 0, P, 1, homs, V, out, false, stream);
+    return render_tex_impl<TexU8>(packed, H, W, P, 0, P, 1, homs, V, out, false, stream);
 }
 
 int mpiv_render_packed_u8_ct(const uint32_t* packed, int H, int W, int P, int p_begin, int p_end, int back,
                              const float* homs, int V, float* ct, void* stream) {
-    return render_u8_impl(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
-}
-
-// ---- half-precision RGBA MPI (render_f16.hip) ----------------------------------------
-
-int mpiv_pack_planes_f16(const uint16_t* mpi, const int64_t st[4], int H, int W, int P, uint16_t* packed,
-                         void* stream) {
-    const char* nm = "mpiv_pack_planes_f16";
-    if (!mpi || !st || !packed) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
-    if (H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
-    if (reinterpret_cast<uintptr_t>(packed) & 7) return fail(MPIV_ERR_ARG, "%s: alignment (packed 8 B)", nm);
-    const int64_t npix = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
-    if (npix * 8 >= (int64_t)kOOB || blocks(P, kPackPl) > kMaxGridYZ)
-        return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or too many planes", nm);
-    const NativeStrides s{0, st[0], st[1], st[2], st[3]};
-    pack_planes_f16_kernel<<<dim3(blocks(npix, kPackPix), blocks(P, kPackPl)), 256, 0, S(stream)>>>(
-        mpi, s, H, W, P, make_fastdiv((unsigned)(W + 2 * kPad)), reinterpret_cast<uint2*>(packed), npix);
-    return launched(nm);
-}
-
-int mpiv_unpack_planes_f16(const uint16_t* packed, int H, int W, int P, float* out, void* stream) {
-    const char* nm = "mpiv_unpack_planes_f16";
-    if (!packed || !out) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
-    if (H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
-    if ((reinterpret_cast<uintptr_t>(packed) & 7) || !aligned16(out))
-        return fail(MPIV_ERR_ARG, "%s: alignment (packed 8 B, out 16 B)", nm);
-    const int64_t n = (int64_t)P * (H + 2 * kPad) * (W + 2 * kPad);
-    const int64_t nb = std::min<int64_t>(blocks(n, 256), 1 << 20);
-    unpack_planes_f16_kernel<<<(unsigned)nb, 256, 0, S(stream)>>>(reinterpret_cast<const uint2*>(packed),
-                                                                 reinterpret_cast<float4*>(out), n);
-    return launched(nm);
-}
-
-static int render_f16_impl(const uint16_t* packed, int H, int W, int P, int p_begin, int p_end, int back,
-                           const float* homs, int V, float* out, bool ct, void* stream) {
-    const char* nm = ct ? "mpiv_render_packed_f16_ct" : "mpiv_render_packed_f16";
-    if (!packed || !homs || !out) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
-    if (V <= 0 || H < 2 || W < 2 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape (H, W >= 2)", nm);
-    if (p_begin < 0 || p_end > P || p_begin >= p_end) return fail(MPIV_ERR_ARG, "%s: bad plane range", nm);
-    if ((reinterpret_cast<uintptr_t>(packed) & 7) || (ct && !aligned16(out)))
-        return fail(MPIV_ERR_ARG, "%s: alignment (packed 8 B, ct 16 B)", nm);
-    const int64_t npix = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
-    if (npix * 8 >= (int64_t)kOOB || H >= (1 << 22) || W >= (1 << 22))
-        return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or a side >= 2^22", nm);
-    const RenderGeom g = make_geom(H, W, P);
-    F16Geom fg;
-    fg.row = g.Wp * 8;
-    fg.org = (kPad * g.Wp + kPad) * 8;
-    fg.plane_bytes = (int)(npix * 8);
-    // The u8 render's dispatch (render_u8_impl): 4 rows per work-item with vertical tap reuse where the
-    // MPI is square or the launch fills the chip (>= 2048 tiles of 64x32), else 2 plain rows; with
-    // reuse, 4 rows in flight when the launch leaves the SIMDs few waves (under 2048 blocks), else 2.
-    const float sxr = (float)W / (float)(H - 1), syr = (float)H / (float)(W - 1);
-    const bool square = sxr >= 0.8f && sxr <= 1.25f && syr >= 0.8f && syr <= 1.25f;
-    const bool big = (int64_t)blocks(W, kTileX) * blocks(H, 4 * 8) * V >= 2048;
-    const bool vs = square || big;
-    const int R = vs ? 4 : 2;
-    const int64_t nb = (int64_t)blocks(W, kTileX) * blocks(H, 4 * R) * V;
-    if (nb > kMaxGridX) return fail(MPIV_ERR_ARG, "%s: too many blocks", nm);
-    const int d = vs && nb < 2048 ? 4 : 2;
-    if (g_route)  // every template argument, as rocprof's demangled name shows it
-        return note_route(nb, 256, "render_f16_kernel<%s, %d, %s, %d>", ct ? "true" : "false", R, vs ? "true" : "false", d);
-    const uint2* pk = reinterpret_cast<const uint2*>(packed);
-    hipStream_t q = S(stream);
-    const int csp = opt(kOptRenderColsep);  // the column-separable issue path (render.hip ColSet)
-    const int ord = render_tile_order(V);
-#define MPIV_F16(CT, RR, VV, DD)                                                                                   \
-    render_f16_kernel<CT, RR, VV, DD><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, fg, V, p_begin, p_end, CT ? back : 1, \
-                                                                   homs, out, csp, ord)
-    if (vs && d == 4) {
-        if (ct) MPIV_F16(true, 4, true, 4);
-        else MPIV_F16(false, 4, true, 4);
-    } else if (vs) {
-        if (ct) MPIV_F16(true, 4, true, 2);
-        else MPIV_F16(false, 4, true, 2);
-    } else if (ct) MPIV_F16(true, 2, false, 2);
-    else MPIV_F16(false, 2, false, 2);
-#undef MPIV_F16
-    return launched(nm);
+    return render_tex_impl<TexU8>(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
 }
 
 int mpiv_render_packed_f16(const uint16_t* packed, int H, int W, int P, const float* homs, int V, float* out,
                            void* stream) {
-    return render_f16_impl(packed, H, W, P, 0, P, 1, homs, V, out, false, stream);
+    return render_tex_impl<TexF16>(packed, H, W, P, 0, P, 1, homs, V, out, false, stream);
 }
 
 int mpiv_render_packed_f16_ct(const uint16_t* packed, int H, int W, int P, int p_begin, int p_end, int back,
                               const float* homs, int V, float* ct, void* stream) {
-    return render_f16_impl(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
+    return render_tex_impl<TexF16>(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
 }
 
 int mpiv_tile_order(int ntiles, int tiles_x, int order, int32_t* out) {
@@ -2374,11 +2339,10 @@ int mpiv_route(const char* entry, const int64_t* a, int na, char* name, int name
         rc = mpiv_render_backward(d, st, (int)a[0], (int)a[1], (int)a[2], (int)P, d, d, ck, d, d,
                                   mpiv_render_backward_workspace_size((int)a[1], (int)a[2], (int)P), nullptr);
     } else if (strcmp(entry, "render_packed_u8") == 0 && na == 4) {
-        rc = render_u8_impl(reinterpret_cast<const uint32_t*>(d), (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d,
-                            (int)a[3], d, false, nullptr);
+        rc = render_tex_impl<TexU8>(d, (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d, false, nullptr);
     } else if ((strcmp(entry, "render_packed_f16") == 0 || strcmp(entry, "render_packed_f16_ct") == 0) && na == 4) {
-        rc = render_f16_impl(reinterpret_cast<const uint16_t*>(d), (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d,
-                             (int)a[3], d, strcmp(entry, "render_packed_f16_ct") == 0, nullptr);
+        rc = render_tex_impl<TexF16>(d, (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d,
+                                     strcmp(entry, "render_packed_f16_ct") == 0, nullptr);
     } else if (strcmp(entry, "render_net_output") == 0 && na == 4) {
         const int64_t B = a[0], H = a[1], W = a[2], P = a[3];
         const int64_t ps[4] = {(2 * P + 3) * H * W, H * W, W, 1}, fs[4] = {H * W * 3, W * 3, 3, 1};

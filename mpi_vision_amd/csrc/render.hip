@@ -1179,15 +1179,29 @@ __global__ __launch_bounds__(256) void render_native_kernel(const float* __restr
 // 2-texel zero border.  A block moves 64 padded pixels x 16 planes through LDS so both
 // sides are coalesced: reads are 16 planes x 16 B = 256 B per pixel, writes 64 pixels
 // x 16 B = 1 KiB per plane; border pixels are written as zeros.
+// T: the texel format -- TexF32 here, TexU8 / TexF16 (render_texel.hip: [P][H+4][W+4] 4- and 8-B
+// texels, the same transpose with a quarter and half of the bytes).  T::gather reads one texel of
+// the view: whole when its channels are contiguous and aligned, else channel by channel.
 // ---------------------------------------------------------------------------
 
 constexpr int kPackPix = 64;
 constexpr int kPackPl = 16;
 
-__global__ __launch_bounds__(256) void pack_planes_kernel(const float* __restrict__ mpi, NativeStrides s,
+struct TexF32 {
+    typedef float Scalar;
+    typedef float4 Texel;
+    static __device__ __forceinline__ float4 gather(const float* src, int64_t sc) {
+        if (sc == 1 && ((reinterpret_cast<uintptr_t>(src) & 15) == 0)) return *reinterpret_cast<const float4*>(src);
+        return make_float4(src[0], src[sc], src[2 * sc], src[3 * sc]);
+    }
+};
+
+template <class T>
+__global__ __launch_bounds__(256) void pack_planes_kernel(const typename T::Scalar* __restrict__ mpi, NativeStrides s,
                                                           int H, int W, int P, FastDiv wp_div,
-                                                          float4* __restrict__ packed, int64_t plane_stride) {
-    __shared__ float4 tile[kPackPl][kPackPix + 1];
+                                                          typename T::Texel* __restrict__ packed,
+                                                          int64_t plane_stride) {
+    __shared__ typename T::Texel tile[kPackPl][kPackPix + 1];
     const int64_t npix = plane_stride;  // (H+4)*(W+4) < 2^27
     const int64_t pix0 = (int64_t)blockIdx.x * kPackPix;
     const int p0 = blockIdx.y * kPackPl;
@@ -1196,18 +1210,12 @@ __global__ __launch_bounds__(256) void pack_planes_kernel(const float* __restric
         const int j = k % kPackPl, i = k / kPackPl;
         const int64_t pix = pix0 + i;
         const int p = p0 + j;
-        float4 val = make_float4(0.f, 0.f, 0.f, 0.f);
+        typename T::Texel val{};  // the border: all-zero bits in every format
         if (pix < npix && p < P) {
             const int yp = (int)fast_div((unsigned)pix, wp_div);
             const int yy = yp - kPad, xx = (int)pix - yp * (int)wp_div.d - kPad;
-            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
-                const float* src = mpi + (int64_t)yy * s.y + (int64_t)xx * s.x + (int64_t)p * s.p;
-                if (s.c == 1 && ((reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
-                    val = *reinterpret_cast<const float4*>(src);
-                } else {
-                    val = make_float4(src[0], src[s.c], src[2 * s.c], src[3 * s.c]);
-                }
-            }
+            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)
+                val = T::gather(mpi + (int64_t)yy * s.y + (int64_t)xx * s.x + (int64_t)p * s.p, s.c);
         }
         tile[j][i] = val;
     }

@@ -179,7 +179,7 @@ def mpi_render_view_u8(rgba_layers_u8, tgt_pose, planes, intrinsics):
     test-MPI format, test/rgba_*.png): returns exactly
     mpi_render_view_torch(rgba_layers_u8.float() / 255.0, tgt_pose, planes, intrinsics)
     (the reference's image convention, utils.py:324-331) without the float copy: each
-    view is packed at 4 B per texel and rendered by render_u8.hip, which converts every
+    view is packed at 4 B per texel and rendered by render_texel.hip, which converts every
     tap to RN(u8/255) exactly before the reference's blend.  Inference only (no autograd:
     uint8 tensors carry no gradient).  An extension of the drop-in API."""
     batch_size = tgt_pose.shape[0]
@@ -208,7 +208,7 @@ def mpi_render_view_f16(rgba_layers_f16, tgt_pose, planes, intrinsics):
     under autocast, an RGBA16F / EXR asset): returns exactly
     mpi_render_view_torch(rgba_layers_f16.float(), tgt_pose, planes, intrinsics)
     in fp32 without the float copy: each view is packed at 8 B per texel and rendered by
-    render_f16.hip, which converts every tap to float (exactly) before the reference's blend.
+    render_texel.hip, which converts every tap to float (exactly) before the reference's blend.
     The packed MPI is a temporary of this call, so a float copy would serve one launch only: a
     stride-0 batch takes the float-copy route of _lib.render_packed_f16 only from
     _lib.F16_FLOAT_ONCE_MIN_VIEWS views, where copy + float kernel beat the f16 kernel; below, and

@@ -244,7 +244,7 @@ def c4n(dev, it, wu):
 
 
 def u8(dev, it, wu):
-    """8-bit RGBA MPIs (render_u8.hip): config 4 at 1 / 8 / 125 views per launch and the
+    """8-bit RGBA MPIs (render_texel.hip): config 4 at 1 / 8 / 125 views per launch and the
     config-5 plane shard, u8 texels (4 B) vs the float path (16 B).  Bytes are the u8
     algorithmic bytes P*H*W*4 + H*W*12 per view (shard: (P/G)*H*W*4 + H*W*16)."""
     c = configs.config4()
