@@ -70,6 +70,7 @@ int mpiv_debug_set(const char *name, int value);
  *   "render_packed_ct_rows"              {H, W, P, V, y_begin, y_end} (mpiv_render_packed_ct_rows)
  *   "render_packed_u8"                   {H, W, P, V}        (mpiv_render_packed_u8)
  *   "render_packed_f16", "render_packed_f16_ct"  {H, W, P, V} (mpiv_render_packed_f16[_ct])
+ *   "render_packed_alpha"                {H, W, P, V}        (mpiv_render_packed_alpha)
  *   "render_net_output"                  {B, H, W, P}        (mpiv_render_net_output)
  *   "render_train"                       {B, H, W, P}        (mpiv_render_train, contiguous MPI)
  *   "render_backward"                    {B, H, W, P}        (mpiv_render_backward, contiguous MPI, the
@@ -482,6 +483,25 @@ int mpiv_render_packed_f16(const uint16_t *packed, int H, int W, int P, const fl
 /* mpiv_render_packed_ct on a packed f16 MPI (plane-range partial (C, T) [V,H,W,4], 16-B aligned). */
 int mpiv_render_packed_f16_ct(const uint16_t *packed, int H, int W, int P, int p_begin, int p_end,
                               int back, const float *homs, int V, float *ct, void *stream);
+
+/* ---- alpha-only MPIs under one constant colour per plane: disparity, depth and coverage maps,
+ * plane-index and tint views.  The frame is defined as mpiv_render_packed on the float MPI whose
+ * RGB is colors[p] at every texel of plane p and whose alpha is the packed channel. -------------- */
+
+/* Channel `channel` (0..3) of one fp32 view [H,W,P,C] (element strides strides[4] = H,W,P,C; the
+ * alpha of an RGBA MPI is channel 3, a [H,W,P,1] tensor's channel 0) -> packed alpha planes
+ * [P][H+4][W+4] float (4-B aligned) with a 2-texel +0 border: mpiv_pack_planes' layout at 4 B per
+ * texel.  Reads only that channel, in place. */
+int mpiv_pack_planes_alpha(const float *mpi_view, const int64_t strides[4], int H, int W, int P, int channel,
+                           float *packed, void *stream);
+
+/* mpiv_render_packed on packed alpha planes and per-plane colours colors [P][3] (device): out
+ * [V,H,W,3] fp32 equals mpiv_render_packed on the float MPI defined above bit for bit -- a colour
+ * tap is colors[p] inside the plane and +0 outside it (the reference's zero padding), blended by
+ * the float kernel's own four-term chain, so -0, Inf and NaN colours propagate as they do there.
+ * The back plane's alpha counts as 1.  H, W >= 2; a padded plane below 2 GiB. */
+int mpiv_render_packed_alpha(const float *packed, int H, int W, int P, const float *colors, const float *homs,
+                             int V, float *out, void *stream);
 
 /* ---- diagnostics ------------------------------------------------------------ */
 

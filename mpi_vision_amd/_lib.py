@@ -99,7 +99,13 @@ _SIGS_CAM = {
     "mpiv_render_backward_cam": [_vp, _c_i64p, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t,
                                  _int, _vp],
 }
-EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + ("mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
+# the alpha-only render under per-plane colours (render_texel.hip TexA32): on their own for the same
+# reason; their side-stream and graph-replay cases are in tests/test_planecolor_gpu.py.
+_SIGS_ALPHA = {
+    "mpiv_pack_planes_alpha": [_vp, _c_i64p, _int, _int, _int, _int, _vp, _vp],
+    "mpiv_render_packed_alpha": [_vp, _int, _int, _int, _vp, _vp, _int, _vp, _vp],
+}
+EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + ("mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
                           "mpiv_render_backward_abort_flag",
                           "mpiv_render_backward_workspace_size_min", "mpiv_render_backward_cam_workspace_size",
                           "mpiv_render_backward_cam_workspace_size_min", "mpiv_build_id", "mpiv_debug_set")
@@ -161,7 +167,7 @@ def _open(path: str, check_id: bool):
                            "(python -c 'import __graft_entry__ as g; g.build()')")
     L.mpiv_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int]
     L.mpiv_debug_set.restype = ctypes.c_int
-    for name, args in (*_SIGS.items(), *_SIGS_CAM.items()):
+    for name, args in (*_SIGS.items(), *_SIGS_CAM.items(), *_SIGS_ALPHA.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int
@@ -687,6 +693,59 @@ def render_packed_f16_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p
                          p_end: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """Plane-range partial (C, T) [V,H,W,4] of a packed f16 MPI (plane sharding)."""
     return _render_views_ct("render_packed_f16_ct", packed, _f16_hw(packed), homs, back, p_begin, p_end, out)
+
+
+def pack_planes_alpha(view: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The alpha of one fp32 MPI view -- channel 3 of [H, W, P, 4], read in place through the view's
+    strides, or a [H, W, P, 1] tensor -- -> packed alpha planes [P, H+4, W+4] float32 with the +0
+    border (the packed u8 layout's geometry: 4 B per texel)."""
+    dev = _dev(view)
+    if view.dim() != 4 or view.shape[3] not in (1, 4):
+        raise RuntimeError(f"pack_planes_alpha expects a [H, W, P, 4] or [H, W, P, 1] tensor, got {tuple(view.shape)}")
+    H, W, P, C = view.shape
+    shape = (P, H + 2 * PAD, W + 2 * PAD)
+    if out is None:
+        packed = torch.empty(shape, device=dev, dtype=torch.float32)
+    else:
+        packed = _check_out(out, shape, dev, "pack_planes_alpha")
+    _call("mpiv_pack_planes_alpha", view, _strides(view), H, W, P, C - 1, packed, _stream(dev))
+    if out is not None:
+        _wrote(packed)
+    return packed
+
+
+def _alpha_hw(packed: torch.Tensor):
+    """(P, H, W) of packed alpha planes, after checking that they are."""
+    _dev(packed)
+    if packed.dim() != 3 or not packed.is_contiguous():
+        raise RuntimeError("packed alpha planes must be a contiguous float32 [P, H+4, W+4] tensor, got "
+                           f"{tuple(packed.shape)}")
+    return packed.shape[0], packed.shape[1] - 2 * PAD, packed.shape[2] - 2 * PAD
+
+
+def render_packed_alpha(packed: torch.Tensor, colors: torch.Tensor, homs: torch.Tensor,
+                        out: torch.Tensor | None = None) -> torch.Tensor:
+    """packed alpha planes [P,H+4,W+4] + one colour per plane `colors` [P,3] + homs [V,P,9] (host or
+    device) -> [V,H,W,3] fp32: bit-identical to render_packed on the float MPI whose RGB is colors[p]
+    all over plane p and whose alpha is the packed channel, from a quarter of its bytes
+    (render_texel.hip TexA32).  A colour tap outside the plane is +0 (the reference's zero padding),
+    so the frame is NOT colour x coverage; -0, Inf and NaN colours propagate as in the float render."""
+    P, H, W = _alpha_hw(packed)
+    dev = packed.device
+    if not isinstance(colors, torch.Tensor) or tuple(colors.shape) != (P, 3):
+        raise RuntimeError(f"render_packed_alpha: colors must be a [{P}, 3] tensor, got "
+                           f"{tuple(colors.shape) if isinstance(colors, torch.Tensor) else type(colors).__name__}")
+    c = _up(colors, dev, "colors")
+    V = homs.shape[0]
+    h = _up(homs.reshape(V, P, 9), dev, "homs")
+    if out is None:
+        out = torch.empty((V, H, W, 3), device=dev, dtype=torch.float32)
+    else:
+        _check_out(out, (V, H, W, 3), dev, "render_packed_alpha")
+    if V == 0:
+        return out
+    _call("mpiv_render_packed_alpha", packed, H, W, P, c, h, V, out, _stream(dev))
+    return out
 
 
 def unpack_planes(packed: torch.Tensor) -> torch.Tensor:

@@ -2283,6 +2283,62 @@ int mpiv_render_packed_f16_ct(const uint16_t* packed, int H, int W, int P, int p
     return render_tex_impl<TexF16>(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
 }
 
+// ---- alpha-only planes under per-plane colours (render_texel.hip TexA32) ----
+
+int mpiv_pack_planes_alpha(const float* mpi, const int64_t st[4], int H, int W, int P, int channel, float* packed,
+                           void* stream) {
+    const char* nm = "mpiv_pack_planes_alpha";
+    if (!mpi || !st || !packed) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if (channel < 0 || channel > 3) return fail(MPIV_ERR_ARG, "%s: channel %d is not in 0..3", nm, channel);
+    if (tex_misaligned<TexA32>(packed)) return fail(MPIV_ERR_ARG, "%s: packed must be 4-byte aligned", nm);
+    const int64_t npix = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
+    if (npix * TexA32::kBytes >= (int64_t)kOOB || blocks(P, kPackPl) > kMaxGridYZ)
+        return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or too many planes", nm);
+    // the transpose of mpiv_pack_planes on one channel: gather reads the word it is pointed at
+    const NativeStrides s{0, st[0], st[1], st[2], st[3]};
+    pack_planes_kernel<TexA32><<<dim3(blocks(npix, kPackPix), blocks(P, kPackPl)), 256, 0, S(stream)>>>(
+        mpi + (int64_t)channel * st[3], s, H, W, P, make_fastdiv((unsigned)(W + 2 * kPad)), packed, npix);
+    return launched(nm);
+}
+
+// The f16 render's dispatch (render_tex_impl without the u8 debug variants): 4 rows per work-item
+// with vertical tap reuse on square-normalised or chip-filling launches, 4 of them in flight while
+// the launch leaves the SIMDs few waves; 2 plain rows on a small stretched launch.
+int mpiv_render_packed_alpha(const float* packed, int H, int W, int P, const float* colors, const float* homs, int V,
+                             float* out, void* stream) {
+    const char* nm = "mpiv_render_packed_alpha";
+    if (!packed || !colors || !homs || !out) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (V <= 0 || H < 2 || W < 2 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape (H, W >= 2)", nm);
+    if (tex_misaligned<TexA32>(packed)) return fail(MPIV_ERR_ARG, "%s: packed must be 4-byte aligned", nm);
+    const int64_t npix = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
+    if (npix * TexA32::kBytes >= (int64_t)kOOB || H >= (1 << 22) || W >= (1 << 22))
+        return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or a side >= 2^22", nm);
+    const RenderGeom g = make_geom(H, W, P);
+    TexGeom tg;
+    tg.row = g.Wp * TexA32::kBytes;
+    tg.org = (kPad * g.Wp + kPad) * TexA32::kBytes;
+    tg.plane_bytes = (int)(npix * TexA32::kBytes);
+    const float sxr = (float)W / (float)(H - 1), syr = (float)H / (float)(W - 1);
+    const bool square = sxr >= 0.8f && sxr <= 1.25f && syr >= 0.8f && syr <= 1.25f;
+    const bool big = (int64_t)blocks(W, kTileX) * blocks(H, 4 * 8) * V >= 2048;
+    const bool vs = square || big;
+    const int R = vs ? 4 : 2;
+    const int64_t nb = (int64_t)blocks(W, kTileX) * blocks(H, 4 * R) * V;
+    if (nb > kMaxGridX) return fail(MPIV_ERR_ARG, "%s: too many blocks", nm);
+    const int d = vs && nb < 2048 ? 4 : 2;
+    if (g_route) return note_route(nb, 256, "render_alpha_kernel<%d, %s, %d>", R, vs ? "true" : "false", d);
+    const int csp = opt(kOptRenderColsep);
+    const int ord = render_tile_order(V);
+#define MPIV_ALPHA(RR, VV, DD) \
+    render_alpha_kernel<RR, VV, DD><<<(unsigned)nb, 256, 0, S(stream)>>>(packed, npix, g, tg, V, colors, homs, out, csp, ord)
+    if (d == 4) MPIV_ALPHA(4, true, 4);
+    else if (vs) MPIV_ALPHA(4, true, 2);
+    else MPIV_ALPHA(2, false, 2);
+#undef MPIV_ALPHA
+    return launched(nm);
+}
+
 int mpiv_tile_order(int ntiles, int tiles_x, int order, int32_t* out) {
     if (!out) return fail(MPIV_ERR_ARG, "mpiv_tile_order: null pointer");
     if (ntiles <= 0 || tiles_x <= 0 || ntiles % tiles_x)
@@ -2343,6 +2399,8 @@ int mpiv_route(const char* entry, const int64_t* a, int na, char* name, int name
     } else if ((strcmp(entry, "render_packed_f16") == 0 || strcmp(entry, "render_packed_f16_ct") == 0) && na == 4) {
         rc = render_tex_impl<TexF16>(d, (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d,
                                      strcmp(entry, "render_packed_f16_ct") == 0, nullptr);
+    } else if (strcmp(entry, "render_packed_alpha") == 0 && na == 4) {
+        rc = mpiv_render_packed_alpha(d, (int)a[0], (int)a[1], (int)a[2], d, d, (int)a[3], d, nullptr);
     } else if (strcmp(entry, "render_net_output") == 0 && na == 4) {
         const int64_t B = a[0], H = a[1], W = a[2], P = a[3];
         const int64_t ps[4] = {(2 * P + 3) * H * W, H * W, W, 1}, fs[4] = {H * W * 3, W * 3, 3, 1};

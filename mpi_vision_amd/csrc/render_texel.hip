@@ -1,5 +1,5 @@
 // render_texel.hip -- the fused warp + over-composite on a narrow-texel RGBA MPI: one schedule,
-// templated on a texel-format trait.  Two formats:
+// templated on a texel-format trait.  Three formats:
 //
 //   TexU8   8-bit RGBA (4-B texels), the reference's own test-MPI format (test/rgba_00..09.png;
 //           utils.py:324-331 reads images as `t.float() / 255.0`).  Packed layout [P][H+4][W+4]
@@ -9,7 +9,14 @@
 //           EXR assets.  Packed layout [P][H+4][W+4][4] half (R in the lowest 16 bits of the texel's
 //           first word): half the HBM bytes and half the memory.
 //
-// Both layouts keep mpiv_pack_planes' plane-major order and 2-texel zero border.
+//   TexA32  the alpha channel alone (4-B fp32 texels) of an MPI whose RGB is one constant colour per
+//           plane: disparity / depth / coverage maps, plane-index and tint views.  Packed layout
+//           [P][H+4][W+4] float -- the u8 layout's geometry, a quarter of the float render's bytes.
+//           The colour is a per-plane uniform ([P,3], loaded with the homography) and its taps load
+//           nothing: a tap is the plane's colour inside the plane and +0 outside (the zero padding
+//           the reference samples), decided from the clamped tap origin the loads use.
+//
+// All layouts keep mpiv_pack_planes' plane-major order and 2-texel zero border.
 //
 // Bit-exactness: a tap's channel is converted to the float texel the reference renders -- exactly
 // (TexU8: RN(u8/255), u8_unit below; TexF16: v_cvt_f32_f16, subnormal halves are normal floats) --
@@ -22,6 +29,9 @@
 // storage of a horizontal tap pair in flight (NW+NE or SW+SE), how a south and a north pair are
 // loaded, the conversion of a pair's channel to float, and (for the pack and float-copy kernels) how
 // a texel is gathered from the caller's [H,W,P,4] view and expanded to a float4.
+// A format may also carry a per-plane context (Ctx, loaded per plane like the homography and handed
+// to chan) and per-tap coverage (kCover: cover() is told which of a pair's columns and whether its
+// row lie inside the plane); TexU8 and TexF16 have neither (an empty Ctx, no cover calls).
 #include "mpiv_common.hpp"
 
 namespace mpiv {
@@ -53,6 +63,9 @@ struct TexU8 {
     typedef uint8_t Scalar;  // a channel of the caller's view
     typedef unsigned Texel;
     static constexpr int kBytes = 4;
+    static constexpr bool kCover = false;
+    struct Ctx {};
+    static __device__ __forceinline__ Ctx load_ctx(const float*, int) { return Ctx{}; }
     struct Pair {
         unsigned l, r;  // the texels at cx and cx + 1: two 4-B loads
     };
@@ -68,7 +81,7 @@ struct TexU8 {
         p.r = __builtin_bit_cast(unsigned, llvm_raw_buffer_load_f32(r, (sh ? kOOB - 4 : off) + 4, 0, 0));
         return p;
     }
-    static __device__ __forceinline__ float chan(const Pair& t, int side, int c) {
+    static __device__ __forceinline__ float chan(const Pair& t, int side, int c, const Ctx&) {
         return u8_unit(((side ? t.r : t.l) >> (8 * c)) & 255u);
     }
     // pack fast path: the 4 bytes of a texel in one aligned word
@@ -86,6 +99,9 @@ struct TexF16 {
     typedef uint16_t Scalar;
     typedef uint2 Texel;
     static constexpr int kBytes = 8;
+    static constexpr bool kCover = false;
+    struct Ctx {};
+    static __device__ __forceinline__ Ctx load_ctx(const float*, int) { return Ctx{}; }
     // A pair is 16 contiguous bytes at an 8-B aligned offset and comes in ONE 16-B buffer load
     // (texel cx in .xy, cx + 1 in .zw) -- half as many gather instructions per plane-sample as the
     // float kernel issues (the measured choice between this and one 8-B load per tap: DESIGN.md §4)
@@ -96,7 +112,7 @@ struct TexF16 {
     static __device__ __forceinline__ Pair load_north(__amdgpu_buffer_rsrc_t r, int off, bool sh) {
         return __builtin_bit_cast(u32x4, llvm_raw_buffer_load_v4f32(r, sh ? kOOB : off, 0, 0));
     }
-    static __device__ __forceinline__ float chan(const Pair& t, int side, int c) {
+    static __device__ __forceinline__ float chan(const Pair& t, int side, int c, const Ctx&) {
         return f16_chan(t[2 * side], t[2 * side + 1], c);
     }
     // pack fast path: the 4 halves of a texel in one aligned 8-B word
@@ -110,6 +126,60 @@ struct TexF16 {
                            f16_chan(t.x, t.y, 3));
     }
 };
+
+// Alpha-only fp32 planes under a constant colour per plane.  The alpha taps are the u8 format's
+// two 4-B words per row; channel c < 3 of a tap is the plane's colour (Ctx) where the tap lies
+// inside the plane and +0 where it does not -- a select, so a colour of -0, Inf or NaN reaches the
+// fma chain exactly as the constructed float MPI's texel (colour inside, zero border outside) does.
+struct TexA32 {
+    typedef float Scalar;
+    typedef float Texel;
+    static constexpr int kBytes = 4;
+    static constexpr bool kCover = true;
+    struct Ctx {
+        float c[3];  // the plane's colour (wave-uniform)
+    };
+    static __device__ __forceinline__ Ctx load_ctx(const float* __restrict__ colors, int p) {
+        Ctx k;
+        k.c[0] = colors[(int64_t)p * 3 + 0];
+        k.c[1] = colors[(int64_t)p * 3 + 1];
+        k.c[2] = colors[(int64_t)p * 3 + 2];
+        return k;
+    }
+    struct Pair {
+        unsigned l, r;  // the alpha words at cx and cx + 1
+        bool il, ir;    // the taps lie inside the plane (cover)
+    };
+    static __device__ __forceinline__ Pair load_south(__amdgpu_buffer_rsrc_t r, int off, int row) {
+        const TexU8::Pair a = TexU8::load_south(r, off, row);
+        return Pair{a.l, a.r, false, false};
+    }
+    static __device__ __forceinline__ Pair load_north(__amdgpu_buffer_rsrc_t r, int off, bool sh) {
+        const TexU8::Pair a = TexU8::load_north(r, off, sh);
+        return Pair{a.l, a.r, false, false};
+    }
+    // xl / xr: column cx / cx + 1 inside [0, W); y: the pair's row inside [0, H)
+    static __device__ __forceinline__ void cover(Pair& t, bool xl, bool xr, bool y) {
+        t.il = xl && y;
+        t.ir = xr && y;
+    }
+    static __device__ __forceinline__ float chan(const Pair& t, int side, int c, const Ctx& k) {
+        if (c == 3) return __builtin_bit_cast(float, side ? t.r : t.l);
+        return (side ? t.ir : t.il) ? k.c[c] : 0.0f;
+    }
+    // pack: `src` points at the channel that is packed (the caller's alpha)
+    static __device__ __forceinline__ Texel gather(const float* src, int64_t) { return *src; }
+};
+
+// Coverage of the two pairs of a tap set from its clamped origin (cx in [-2, W], cy in [-2, H]; the
+// clamp moves no tap across the plane's edge): column cx is inside iff 0 <= cx <= W-1, column cx + 1
+// iff -1 <= cx <= W-2; the north row is cy, the south row cy + 1.
+template <class T>
+__device__ __forceinline__ void cover_taps(typename T::Pair& n, typename T::Pair& s, int cx, int cy, int W, int H) {
+    const bool xl = (unsigned)cx < (unsigned)W, xr = (unsigned)(cx + 1) < (unsigned)W;
+    T::cover(n, xl, xr, (unsigned)cy < (unsigned)H);
+    T::cover(s, xl, xr, (unsigned)(cy + 1) < (unsigned)H);
+}
 
 struct TexGeom {
     int org;          // byte offset of texel (0, 0) in a padded plane
@@ -135,20 +205,21 @@ __device__ __forceinline__ void issue_taps_tex(__amdgpu_buffer_rsrc_t r, int W, 
     const int off = (__mul24(cy, Wp) + cx) * T::kBytes + org;  // >= 0, <= plane bytes - row - 2 texels
     t.n = T::load_north(r, off, false);
     t.s = T::load_south(r, off, row);
+    if constexpr (T::kCover) cover_taps<T>(t.n, t.s, cx, cy, W, H);
 }
 
 // blend_taps with the same weight products (issue_taps_padded) and fma chain
 template <class T>
-__device__ __forceinline__ f32x4 blend_taps_tex(const TapSetTex<T>& t) {
+__device__ __forceinline__ f32x4 blend_taps_tex(const TapSetTex<T>& t, const typename T::Ctx& kc) {
     const float ex = 1.0f - t.wx, sy = 1.0f - t.wy;
     const float nw = sy * ex, ne = sy * t.wx, sw = t.wy * ex, se = t.wy * t.wx;
     f32x4 o;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        float acc = T::chan(t.n, 0, k) * nw;
-        acc = __builtin_fmaf(T::chan(t.n, 1, k), ne, acc);
-        acc = __builtin_fmaf(T::chan(t.s, 0, k), sw, acc);
-        acc = __builtin_fmaf(T::chan(t.s, 1, k), se, acc);
+        float acc = T::chan(t.n, 0, k, kc) * nw;
+        acc = __builtin_fmaf(T::chan(t.n, 1, k, kc), ne, acc);
+        acc = __builtin_fmaf(T::chan(t.s, 0, k, kc), sw, acc);
+        acc = __builtin_fmaf(T::chan(t.s, 1, k, kc), se, acc);
         o[k] = acc;
     }
     return o;
@@ -156,11 +227,12 @@ __device__ __forceinline__ f32x4 blend_taps_tex(const TapSetTex<T>& t) {
 
 // a pair's two texels as floats
 template <class T>
-__device__ __forceinline__ void cvt_pair(const typename T::Pair& t, f32x4& l, f32x4& r) {
+__device__ __forceinline__ void cvt_pair(const typename T::Pair& t, const typename T::Ctx& kc, f32x4& l,
+                                         f32x4& r) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        l[c] = T::chan(t, 0, c);
-        r[c] = T::chan(t, 1, c);
+        l[c] = T::chan(t, 0, c, kc);
+        r[c] = T::chan(t, 1, c, kc);
     }
 }
 
@@ -170,13 +242,15 @@ __device__ __forceinline__ void cvt_pair(const typename T::Pair& t, f32x4& l, f3
 template <class T, bool CT, bool GUARD, int R>
 __device__ __forceinline__ void render_tex_pixels(const typename T::Texel* __restrict__ planes, int64_t plane_stride,
                                                   const RenderGeom& g, const TexGeom& tg, int p_begin, int p_end,
-                                                  int back, const float* __restrict__ hv, int x, int y0, float* cr,
+                                                  int back, const float* __restrict__ hv,
+                                                  const float* __restrict__ colors, int x, int y0, float* cr,
                                                   float* cg, float* cb, float* tt) {
     static_assert(R % 2 == 0, "R must be even");
     const float fx = (float)x;
     const bool replace_first = !CT || back;
     const int last = p_end - 1;
     auto hom = [&](int p) { return load_hom(hv + (int64_t)(p < last ? p : last) * 9); };
+    auto ctx = [&](int p) { return T::load_ctx(colors, p < last ? p : last); };
     auto issue = [&](int p, int k, const Hom9& h, TapSetTex<T>& ts) {
         const int q = p < last ? p : last;
         float px, py;
@@ -184,8 +258,8 @@ __device__ __forceinline__ void render_tex_pixels(const typename T::Texel* __res
         issue_taps_tex<T>(make_rsrc(planes + (int64_t)q * plane_stride, tg.plane_bytes), g.W, g.H, g.Wp, tg.org,
                           tg.row, px, py, ts);
     };
-    auto consume = [&](const TapSetTex<T>& ts, int k, bool first) {
-        const f32x4 s = blend_taps_tex<T>(ts);
+    auto consume = [&](const TapSetTex<T>& ts, const typename T::Ctx& kc, int k, bool first) {
+        const f32x4 s = blend_taps_tex<T>(ts, kc);
         const float a = first ? 1.0f : s[3];
         const float om = 1.0f - a;
         cr[k] = over(s[0], a, om, cr[k]);
@@ -195,6 +269,7 @@ __device__ __forceinline__ void render_tex_pixels(const typename T::Texel* __res
     };
     TapSetTex<T> A, B;
     Hom9 h = hom(p_begin), hn = hom(p_begin + 1);
+    typename T::Ctx kc = ctx(p_begin), kn = ctx(p_begin + 1);  // the colours of the plane consumed / the next
     issue(p_begin, 0, h, A);
     for (int p = p_begin; p < p_end; ++p) {
         const bool first = replace_first && p == p_begin;
@@ -202,16 +277,18 @@ __device__ __forceinline__ void render_tex_pixels(const typename T::Texel* __res
         for (int k = 0; k < R; k += 2) {  // A holds (p, k)
             issue(p, k + 1, h, B);
             __builtin_amdgcn_sched_barrier(0);
-            consume(A, k, first);
+            consume(A, kc, k, first);
             if (k + 2 < R)
                 issue(p, k + 2, h, A);
             else
                 issue(p + 1, 0, hn, A);  // past the end: the last plane again (cached, unused)
             __builtin_amdgcn_sched_barrier(0);
-            consume(B, k + 1, first);
+            consume(B, kc, k + 1, first);
         }
         h = hn;
         hn = hom(p + 2);
+        kc = kn;
+        kn = ctx(p + 2);
     }
 }
 
@@ -230,7 +307,8 @@ template <class T, bool CT, bool GUARD, int R, int D = 2, bool CS = false>
 __device__ __forceinline__ void render_tex_vs_pixels(const typename T::Texel* __restrict__ planes,
                                                      int64_t plane_stride, const RenderGeom& g, const TexGeom& tg,
                                                      int p_begin, int p_end, int back, const float* __restrict__ hv,
-                                                     int x, int y0, float* cr, float* cg, float* cb, float* tt) {
+                                                     const float* __restrict__ colors, int x, int y0, float* cr,
+                                                     float* cg, float* cb, float* tt) {
     static_assert(R % 2 == 0, "R must be even");
     struct Row {
         typename T::Pair n, s;  // NW+NE (own, when not shared) and SW+SE texel pairs
@@ -242,14 +320,19 @@ __device__ __forceinline__ void render_tex_vs_pixels(const typename T::Texel* __
     const bool replace_first = !CT || back;
     const int last = p_end - 1;
     auto hom = [&](int p) { return load_hom(hv + (int64_t)(p < last ? p : last) * 9); };
+    auto ctx = [&](int p) { return T::load_ctx(colors, p < last ? p : last); };
     static_assert(!CS || !GUARD, "the column set shares one proven division");
     [[maybe_unused]] ColSet col;  // CS: the plane being issued (can_share is false at a plane's first row)
+    [[maybe_unused]] int ccx = 0;  // kCover: the tap column cx (CS: of the plane being issued)
     auto issue = [&](int p, int k, const Hom9& h, int prev_off, bool can_share, Row& t) {
         const int q = p < last ? p : last;
         float py;
         int off;
         if constexpr (CS) {
-            if (!can_share) col = col_setup<T::kBytes>(h.h, fx, (float)y0, g, tg.org);
+            if (!can_share) {
+                col = col_setup<T::kBytes>(h.h, fx, (float)y0, g, tg.org);
+                if constexpr (T::kCover) ccx = (col.coff - tg.org) / T::kBytes;  // exact: coff = cx * kBytes + org
+            }
             py = col_row_py(h.h, fx, (float)(y0 + k), col, g);
             t.wx = col.wx;
         } else {
@@ -258,6 +341,7 @@ __device__ __forceinline__ void render_tex_vs_pixels(const typename T::Texel* __
             const float fx0 = floorf(px);
             t.wx = px - fx0;
             off = (int)__builtin_amdgcn_fmed3f(fx0, -2.0f, (float)g.W);  // cx
+            if constexpr (T::kCover) ccx = off;
         }
         const float fy0 = floorf(py);
         t.wy = py - fy0;
@@ -273,15 +357,18 @@ __device__ __forceinline__ void render_tex_vs_pixels(const typename T::Texel* __
         t.own = __builtin_amdgcn_ballot_w64(!t.sh) != 0;
         if (t.own)  // wave-uniform: some lane needs its own north pair
             t.n = T::load_north(r, off, t.sh);
+        // (a shared north pair is the previous row's south pair, coverage included: the same texels)
+        if constexpr (T::kCover) cover_taps<T>(t.n, t.s, ccx, cy, g.W, g.H);
     };
     // pc, pd: the previous row's converted south taps; sc, sd: this row's (out)
-    auto consume = [&](const Row& t, const f32x4& pc, const f32x4& pd, int k, bool first, f32x4& sc, f32x4& sd) {
-        cvt_pair<T>(t.s, sc, sd);
+    auto consume = [&](const Row& t, const typename T::Ctx& kc, const f32x4& pc, const f32x4& pd, int k, bool first,
+                       f32x4& sc, f32x4& sd) {
+        cvt_pair<T>(t.s, kc, sc, sd);
         f32x4 na = pc, nb = pd;
         if (t.own) {
             asm volatile("");  // a real wave-uniform branch (render.hip MPIV_VS_ASMBR)
             f32x4 ua, ub;
-            cvt_pair<T>(t.n, ua, ub);
+            cvt_pair<T>(t.n, kc, ua, ub);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 na[c] = t.sh ? pc[c] : ua[c];
@@ -316,6 +403,7 @@ __device__ __forceinline__ void render_tex_vs_pixels(const typename T::Texel* __
         constexpr int AHEAD = D - 1;             // rows issued ahead of the one consumed
         Row ring[D];
         Hom9 hq[NH];
+        typename T::Ctx kq[2] = {ctx(p_begin), ctx(p_begin + 1)};  // the plane consumed and the next
 #pragma unroll
         for (int j = 0; j < NH; ++j) hq[j] = hom(p_begin + j);
 #pragma unroll
@@ -337,18 +425,21 @@ __device__ __forceinline__ void render_tex_vs_pixels(const typename T::Texel* __
                     asm volatile("" ::: "memory");
                     __builtin_amdgcn_sched_barrier(0);
                     f32x4 sc, sd;
-                    consume(ring[it % D], pc, pd, k, first, sc, sd);
+                    consume(ring[it % D], kq[0], pc, pd, k, first, sc, sd);
                     pc = sc;
                     pd = sd;
                 }
 #pragma unroll
                 for (int j = 0; j + 1 < NH; ++j) hq[j] = hq[j + 1];
                 hq[NH - 1] = hom(pu + NH);
+                kq[0] = kq[1];
+                kq[1] = ctx(pu + 2);
             }
         }
         return;
     }
     Hom9 h = hom(p_begin), hn = hom(p_begin + 1);
+    typename T::Ctx kc = ctx(p_begin), kn = ctx(p_begin + 1);
     Row A, B;
     issue(p_begin, 0, h, 0, false, A);
     for (int p = p_begin; p < p_end; ++p) {
@@ -359,7 +450,7 @@ __device__ __forceinline__ void render_tex_vs_pixels(const typename T::Texel* __
             asm volatile("" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
             f32x4 sc, sd;
-            consume(A, pc, pd, k, first, sc, sd);
+            consume(A, kc, pc, pd, k, first, sc, sd);
             pc = sc;
             pd = sd;
             if (k + 2 < R)
@@ -368,12 +459,14 @@ __device__ __forceinline__ void render_tex_vs_pixels(const typename T::Texel* __
                 issue(p + 1, 0, hn, 0, false, A);  // past the end: the last plane again (cached, unused)
             asm volatile("" ::: "memory");
             __builtin_amdgcn_sched_barrier(0);
-            consume(B, pc, pd, k + 1, first, sc, sd);
+            consume(B, kc, pc, pd, k + 1, first, sc, sd);
             pc = sc;
             pd = sd;
         }
         h = hn;
         hn = hom(p + 2);
+        kc = kn;
+        kn = ctx(p + 2);
     }
 }
 
@@ -385,7 +478,7 @@ template <class T, bool CT, int R, bool VS, int D>
 __device__ __forceinline__ void render_tex_tile(const typename T::Texel* __restrict__ planes, int64_t plane_stride,
                                                 const RenderGeom& g, const TexGeom& tg, int V, int p_begin, int p_end,
                                                 int back, const float* __restrict__ homs, float* __restrict__ out,
-                                                int colsep, int order) {
+                                                int colsep, int order, const float* __restrict__ colors = nullptr) {
     constexpr int TY = 4 * R;
     const int tiles_x = (g.W + kTileX - 1) / kTileX;
     const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
@@ -428,17 +521,17 @@ __device__ __forceinline__ void render_tex_tile(const typename T::Texel* __restr
         if constexpr (VS) {
             if (sep)  // block-uniform
                 render_tex_vs_pixels<T, CT, false, R, D, true>(planes, plane_stride, g, tg, p_begin, p_end, back, hv,
-                                                               x, y0, cr, cg, cb, tt);
+                                                               colors, x, y0, cr, cg, cb, tt);
             else
-                render_tex_vs_pixels<T, CT, false, R, D>(planes, plane_stride, g, tg, p_begin, p_end, back, hv, x, y0,
-                                                         cr, cg, cb, tt);
+                render_tex_vs_pixels<T, CT, false, R, D>(planes, plane_stride, g, tg, p_begin, p_end, back, hv, colors,
+                                                         x, y0, cr, cg, cb, tt);
         } else
-            render_tex_pixels<T, CT, false, R>(planes, plane_stride, g, tg, p_begin, p_end, back, hv, x, y0, cr, cg,
-                                               cb, tt);
+            render_tex_pixels<T, CT, false, R>(planes, plane_stride, g, tg, p_begin, p_end, back, hv, colors, x, y0, cr,
+                                               cg, cb, tt);
     } else {  // rare (w near 0 over the tile): the guarded recipe two rows at a time (few VGPRs)
 #pragma unroll
         for (int k = 0; k < R; k += 2)
-            render_tex_pixels<T, CT, true, 2>(planes, plane_stride, g, tg, p_begin, p_end, back, hv, x, y0 + k,
+            render_tex_pixels<T, CT, true, 2>(planes, plane_stride, g, tg, p_begin, p_end, back, hv, colors, x, y0 + k,
                                               cr + k, cg + k, cb + k, tt + k);
     }
 #pragma unroll
@@ -473,6 +566,18 @@ __global__ __launch_bounds__(256) void render_f16_kernel(const uint2* __restrict
                                                          float* __restrict__ out, int colsep = 0, int order = 0) {
     render_tex_tile<TexF16, CT, R, VS, D>(planes, plane_stride, g, tg, V, p_begin, p_end, back, homs, out, colsep,
                                           order);
+}
+
+// Alpha-only planes under per-plane colours [P,3] (TexA32): the full composite only (no (C, T)
+// partials), so the template arguments are the rows per work-item, the reuse and the rows in flight.
+template <int R, bool VS = false, int D = 2>
+__global__ __launch_bounds__(256) void render_alpha_kernel(const float* __restrict__ planes, int64_t plane_stride,
+                                                           RenderGeom g, TexGeom tg, int V,
+                                                           const float* __restrict__ colors,
+                                                           const float* __restrict__ homs, float* __restrict__ out,
+                                                           int colsep = 0, int order = 0) {
+    render_tex_tile<TexA32, false, R, VS, D>(planes, plane_stride, g, tg, V, 0, g.P, 1, homs, out, colsep, order,
+                                             colors);
 }
 
 // Packed narrow planes -> packed float planes (the same padded [P][H+4][W+4] layout as

@@ -239,6 +239,77 @@ def mpi_render_view_f16(rgba_layers_f16, tgt_pose, planes, intrinsics):
     return out
 
 
+def _plane_color_mpi(rgba_layers, plane_colors):
+    """The float MPI the plane-colour render is defined on: RGB = plane_colors[p] all over plane p,
+    alpha = rgba_layers' last channel (torch ops: differentiable w.r.t. both)."""
+    B, H, W, P, _ = rgba_layers.shape
+    rgb = plane_colors.to(rgba_layers.device)[None, None, None].expand(B, H, W, P, 3)
+    return torch.cat([rgb, rgba_layers[..., -1:]], -1)
+
+
+def mpi_render_plane_colors_torch(rgba_layers, plane_colors, tgt_pose, planes, intrinsics):
+    """Composite one constant colour per plane, plane_colors [P, 3], through an MPI's alpha:
+    returns exactly (bit for bit)
+
+        mpi_render_view_torch(cat([plane_colors[None, None, None].expand(B, H, W, P, 3),
+                                   rgba_layers[..., -1:]], -1), tgt_pose, planes, intrinsics)
+
+    in [B, H, W, 3] fp32 without building that MPI.  rgba_layers is [B, H, W, P, 4] fp32 -- only
+    channel 3 is read, in place through its strides -- or an alpha-only [B, H, W, P, 1].  Each view's
+    alpha is packed at 4 B per texel and rendered by render_texel.hip's alpha format: a quarter of the
+    float render's bytes.  As in the reference, a colour tap outside the plane contributes 0 (zero
+    padding), so the result is not colour x coverage, and the back plane's alpha counts as 1.  Poses
+    may live on the host or the device; a stride-0 batch is packed once and rendered in one launch.
+
+    Autograd: when rgba_layers, plane_colors, tgt_pose, planes or intrinsics requires grad (and grad
+    is enabled), the constant-colour MPI IS built with torch ops and rendered by the differentiable
+    mpi_render_view_torch -- the reference's gradients, at the cost of the float MPI's memory
+    (16 B per texel).  An extension of the drop-in API."""
+    batch_size = tgt_pose.shape[0]
+    n_planes = len(planes)
+    depths = planes.reshape([n_planes, 1])  # AttributeError on a list, like the reference
+    if not isinstance(rgba_layers, torch.Tensor) or rgba_layers.dtype != torch.float32:
+        raise RuntimeError(f"expected scalar type Float but found {getattr(rgba_layers, 'dtype', type(rgba_layers))}")
+    if rgba_layers.dim() != 5 or rgba_layers.shape[-1] not in (1, 4):
+        raise RuntimeError(f"expected a [B, H, W, P, 4] or [B, H, W, P, 1] MPI, got {tuple(rgba_layers.shape)}")
+    _lib._dev(rgba_layers)  # no CPU path
+    B, H, W, P, _ = rgba_layers.shape
+    if B != batch_size or P != n_planes or tuple(plane_colors.shape) != (P, 3):
+        raise RuntimeError(f"shape mismatch: MPI batch/planes {B}/{P} vs poses/planes {batch_size}/{n_planes}, "
+                           f"plane_colors {tuple(plane_colors.shape)}")
+    if torch.is_grad_enabled() and (rgba_layers.requires_grad or plane_colors.requires_grad
+                                    or _camera_grad(tgt_pose, planes, intrinsics)):
+        return mpi_render_view_torch(_plane_color_mpi(rgba_layers, plane_colors), tgt_pose, planes, intrinsics)
+    if tgt_pose.is_cuda:
+        homs = _host.render_homographies_device(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
+    else:
+        _lib.host_under_capture("tgt_pose")
+        homs = _host.render_homographies(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
+    homs = homs.reshape(B, P, 9)
+    colors = _lib._up(plane_colors.detach(), rgba_layers.device, "plane_colors")
+    if B > 1 and rgba_layers.stride(0) == 0:  # one MPI, many views: pack once
+        return _lib.render_packed_alpha(_lib.pack_planes_alpha(rgba_layers[0]), colors, homs)
+    out = torch.empty((B, H, W, 3), device=rgba_layers.device, dtype=torch.float32)
+    packed = None
+    for b in range(B):
+        packed = _lib.pack_planes_alpha(rgba_layers[b], out=packed)
+        _lib.render_packed_alpha(packed, colors, homs[b:b + 1], out=out[b:b + 1])
+    return out
+
+
+def mpi_render_depth_torch(rgba_layers, tgt_pose, planes, intrinsics):
+    """Disparity, depth and coverage of a rendered view, [B, H, W, 3] fp32: channel 0 the expected
+    inverse depth, channel 1 the expected depth, channel 2 the accumulated coverage -- exactly
+    mpi_render_plane_colors_torch(rgba_layers, stack([1.0 / planes, planes, ones_like(planes)], -1),
+    tgt_pose, planes, intrinsics).  As in the reference's over_composite the back plane's alpha counts
+    as 1; coverage falls below 1 only where taps leave the planes.  Same inputs, routes and autograd
+    rule as mpi_render_plane_colors_torch.  An extension of the drop-in API."""
+    n_planes = len(planes)
+    d = planes.reshape([n_planes])  # AttributeError on a list, like the reference
+    colors = torch.stack([1.0 / d, d, torch.ones_like(d)], -1)
+    return mpi_render_plane_colors_torch(rgba_layers, colors, tgt_pose, planes, intrinsics)
+
+
 def mpi_from_net_output(mpi_pred, dep):
     """The notebook's MPI assembly (fast-torch-stereo-vision.ipynb cell 10 L79-111):
     the network output [B, 2P+3, H, W] (P blend weights, P alphas, background rgb) and

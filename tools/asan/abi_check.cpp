@@ -108,6 +108,40 @@ int main() {
         EXPECT(mpiv_route("render_packed_f16_ct", a4, 4, name, sizeof(name), &grid) == MPIV_OK);
         EXPECT(std::strncmp(name, "render_f16_kernel<true", 22) == 0);
     }
+    // alpha-only planes under per-plane colours: null pointers, shapes, channel, alignment (packed 4 B), plane size
+    {
+        float* f2 = reinterpret_cast<float*>(2);
+        EXPECT(mpiv_pack_planes_alpha(nullptr, st4, 4, 4, 2, 3, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_pack_planes_alpha(f, nullptr, 4, 4, 2, 3, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_pack_planes_alpha(f, st4, 4, 4, 2, 3, nullptr, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "null pointer") != nullptr);
+        EXPECT(mpiv_pack_planes_alpha(f, st4, 4, 4, 0, 3, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "bad shape") != nullptr);
+        EXPECT(mpiv_pack_planes_alpha(f, st4, 4, 4, 2, 4, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_pack_planes_alpha(f, st4, 4, 4, 2, -1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "channel") != nullptr);
+        EXPECT(mpiv_pack_planes_alpha(f, st4, 4, 4, 2, 3, f2, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "4-byte aligned") != nullptr);
+        EXPECT(mpiv_pack_planes_alpha(f, st4, 24000, 24000, 2, 3, f, nullptr) == MPIV_ERR_ARG);  // plane >= 2 GiB
+        EXPECT(mpiv_render_packed_alpha(nullptr, 4, 4, 2, f, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_alpha(f, 4, 4, 2, nullptr, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_alpha(f, 4, 4, 2, f, nullptr, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_alpha(f, 4, 4, 2, f, f, 1, nullptr, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "null pointer") != nullptr);
+        EXPECT(mpiv_render_packed_alpha(f, 1, 4, 2, f, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_alpha(f, 4, 4, 0, f, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(mpiv_render_packed_alpha(f, 4, 4, 2, f, f, 0, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "bad shape") != nullptr);
+        EXPECT(mpiv_render_packed_alpha(f2, 4, 4, 2, f, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "4-byte aligned") != nullptr);
+        EXPECT(mpiv_render_packed_alpha(f, 24000, 24000, 2, f, f, 1, f, nullptr) == MPIV_ERR_ARG);
+        EXPECT(std::strstr(mpiv_last_error(), "2 GiB") != nullptr);
+        char name[160];
+        int64_t grid = 0;
+        const int64_t a4[4] = {1024, 1024, 128, 1};
+        EXPECT(mpiv_route("render_packed_alpha", a4, 4, name, sizeof(name), &grid) == MPIV_OK);
+        EXPECT(std::strcmp(name, "render_alpha_kernel<4, true, 4>") == 0 && grid == 16 * 64 * 256);
+    }
     // the tile order on an exact-size heap buffer: a permutation; bad arguments rejected
     {
         std::vector<int32_t> ord(9 * 5);
