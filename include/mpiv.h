@@ -253,6 +253,31 @@ int mpiv_render_backward_cam(const float *mpi, const int64_t mpi_strides[5], int
 size_t mpiv_render_backward_cam_workspace_size(int H, int W, int P);
 size_t mpiv_render_backward_cam_workspace_size_min(int H, int W, int P);
 
+/* ---- training through a half-precision MPI, read in place ----------------
+ * The four entries above for rgba_layers in IEEE half (the MPI a network emits under autocast): mpi and
+ * dmpi are [.][H][W][P][4] half, mpi_strides are in HALF elements, and the layout rule is 8-byte aligned
+ * texels with strides[3] == 4 and strides[4] == 1 (row and pixel strides below 2^22 texels, as above).
+ * Every tap is one 8-byte load of 4 halves, converted to float (exactly) before the float kernels' own
+ * arithmetic, so frames, checkpoints and dhoms are bit-identical to the float entries' on the widened
+ * MPI; dmpi is that call's fp32 gradient rounded to half once per texel channel (IEEE round-to-nearest-
+ * even: overflow gives +-inf, half subnormals are kept, -0 and NaN preserved), 8-byte aligned, one
+ * gradient per view.  out, ckpt, homs, dout, dhoms and the workspace are fp32 as above and the workspace
+ * sizes are the float entries' (the same size queries serve).  A view stays on 32-bit tap offsets while
+ * it spans less than 2 GiB -- twice the float texel count -- and takes the 64-bit tap readers beyond.
+ * mpiv_debug_set("bwd_gather", k != 0) (A/B gathers, fp32 gradients only) makes them fail. */
+int mpiv_render_train_f16(const uint16_t *mpi, const int64_t mpi_strides[5], int B, int H, int W, int P,
+                          const float *homs, float *out, float *ckpt, void *stream);
+int mpiv_render_backward_f16(const uint16_t *mpi, const int64_t mpi_strides[5], int V, int H, int W, int P,
+                             const float *homs, const float *dout, const float *ckpt, uint16_t *dmpi,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int mpiv_render_backward_watched_f16(const uint16_t *mpi, const int64_t mpi_strides[5], int V, int H, int W,
+                                     int P, const float *homs, const float *dout, const float *ckpt,
+                                     uint16_t *dmpi, void *workspace, size_t workspace_bytes, void *stream);
+int mpiv_render_backward_cam_f16(const uint16_t *mpi, const int64_t mpi_strides[5], int V, int H, int W, int P,
+                                 const float *homs, const float *dout, const float *ckpt, uint16_t *dmpi,
+                                 float *dhoms, void *workspace, size_t workspace_bytes, int watched,
+                                 void *stream);
+
 /* ---- MPI assembly from the network output ------------------------------- */
 
 /* mpi_from_net_output (fast-torch-stereo-vision.ipynb cell 10 L79-111): the network's

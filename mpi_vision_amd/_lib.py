@@ -105,7 +105,16 @@ _SIGS_ALPHA = {
     "mpiv_pack_planes_alpha": [_vp, _c_i64p, _int, _int, _int, _int, _vp, _vp],
     "mpiv_render_packed_alpha": [_vp, _int, _int, _int, _vp, _vp, _int, _vp, _vp],
 }
-EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + ("mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
+# training through a half MPI read in place (render_chunk.hip InF16): the float entries' arguments with
+# half rgba_layers / d rgba_layers; on their own for the same reason, their side-stream and graph-replay
+# cases are in tests/test_f16_train_gpu.py.
+_SIGS_F16_TRAIN = {
+    "mpiv_render_train_f16": _SIGS["mpiv_render_train"],
+    "mpiv_render_backward_f16": _SIGS["mpiv_render_backward"],
+    "mpiv_render_backward_watched_f16": _SIGS["mpiv_render_backward_watched"],
+    "mpiv_render_backward_cam_f16": _SIGS_CAM["mpiv_render_backward_cam"],
+}
+EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_F16_TRAIN) + ("mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
                           "mpiv_render_backward_abort_flag",
                           "mpiv_render_backward_workspace_size_min", "mpiv_render_backward_cam_workspace_size",
                           "mpiv_render_backward_cam_workspace_size_min", "mpiv_build_id", "mpiv_debug_set")
@@ -167,7 +176,7 @@ def _open(path: str, check_id: bool):
                            "(python -c 'import __graft_entry__ as g; g.build()')")
     L.mpiv_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int]
     L.mpiv_debug_set.restype = ctypes.c_int
-    for name, args in (*_SIGS.items(), *_SIGS_CAM.items(), *_SIGS_ALPHA.items()):
+    for name, args in (*_SIGS.items(), *_SIGS_CAM.items(), *_SIGS_ALPHA.items(), *_SIGS_F16_TRAIN.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int
@@ -330,8 +339,9 @@ def _strides(t: torch.Tensor, dims=None):
     return (ctypes.c_int64 * len(st))(*st)
 
 
-def _dev(*tensors):
-    """All tensors must be fp32 on one ROCm device; returns that device."""
+def _dev(*tensors, f16_first: bool = False):
+    """All tensors must be fp32 on one ROCm device; returns that device.  f16_first: the first one (the
+    MPI of the training entries) may be float16 instead."""
     dev = None
     for t in tensors:
         if not isinstance(t, torch.Tensor):
@@ -339,7 +349,7 @@ def _dev(*tensors):
         if t.device.type != "cuda":
             raise RuntimeError("mpi_vision_amd kernels need ROCm device tensors "
                                f"(got a tensor on {t.device}); there is no CPU path")
-        if t.dtype != torch.float32:
+        if t.dtype != torch.float32 and not (f16_first and t is tensors[0] and t.dtype == torch.float16):
             raise RuntimeError(f"expected scalar type Float but found {t.dtype}")
         if dev is None:
             dev = t.device
@@ -829,12 +839,29 @@ def render(rgba_layers: torch.Tensor, homs: torch.Tensor) -> torch.Tensor:
 def bwd_layout_ok(rgba_layers: torch.Tensor) -> bool:
     """True when mpiv_render_backward reads this [B,H,W,P,4] tensor in place (abi.hip:
     16-B texels with planes contiguous per pixel, row and pixel strides below 2^22 texels; a
-    view of 2 GiB or more is read through 64-bit tap addresses, so its span is not limited)."""
+    view of 2 GiB or more is read through 64-bit tap addresses, so its span is not limited).
+    A float16 tensor: the same limits for mpiv_render_backward_f16, with 8-B aligned texels."""
     B, H, W, P, C = rgba_layers.shape
     st = rgba_layers.stride()
     if C != 4 or st[4] != 1 or st[3] != 4 or any(s % 4 for s in st[:3]) or st[1] < 0 or st[2] < 0:
         return False
-    return rgba_layers.data_ptr() % 16 == 0 and st[1] // 4 < (1 << 22) and st[2] // 4 < (1 << 22)
+    texel = 4 * rgba_layers.element_size()
+    return rgba_layers.data_ptr() % texel == 0 and st[1] // 4 < (1 << 22) and st[2] // 4 < (1 << 22)
+
+
+def _f16(t: torch.Tensor) -> bool:
+    """A half MPI: the _f16 twins of the training entries (render_chunk.hip InF16) serve it."""
+    return t.dtype == torch.float16
+
+
+def _f16_in_place(t: torch.Tensor) -> torch.Tensor:
+    """The half tensor itself where mpiv_render_*_f16 read it in place, else a contiguous HALF copy (never
+    a float one); a densely laid out tensor whose data pointer is not 8-byte aligned is its own
+    .contiguous(), so that one is cloned."""
+    if bwd_layout_ok(t):
+        return t
+    c = t.contiguous()
+    return c if c.data_ptr() % 8 == 0 else c.clone()
 
 
 def train_layout_ok(rgba_layers: torch.Tensor) -> bool:
@@ -857,10 +884,27 @@ def render_train(rgba_layers: torch.Tensor, homs: torch.Tensor, broadcast_in_pla
     mpiv_render_train -- frames bit-identical to render() -- or (render(), None) when the
     layout is not read in place (a broadcast batch renders from one packed copy instead, unless
     broadcast_in_place: the camera gradient's backward wants the checkpoints of every view)."""
-    dev = _dev(rgba_layers)
+    dev = _dev(rgba_layers, f16_first=True)
     B, H, W, P, _ = rgba_layers.shape
     if homs.shape[0] != B or homs.shape[1] != P:
         raise RuntimeError(f"shape mismatch: MPI batch/planes {B}/{P} vs poses/planes {homs.shape[0]}/{homs.shape[1]}")
+    if _f16(rgba_layers):
+        # a half MPI (mpiv_render_train_f16, fp32 frames and checkpoints): there is no packed half route
+        # with checkpoints, so a broadcast batch is read in place too, and any other layout through a
+        # contiguous HALF copy -- never a float one.  Past the in-place limits the frame alone comes without
+        # checkpoints: a degenerate frame (H or W < 2, which the packed f16 render does not take either)
+        # from the float render on a widened copy of its one row or column, anything else (P > 796, the
+        # backward's size ceiling) from the packed f16 render; the backward reads the half tensor in place.
+        if H < 2 or W < 2:
+            return render(rgba_layers.float(), homs), None
+        if not (4 * 64 * 9 * 16 + P * 36 <= _CHUNK_LDS and H * W < (1 << 26) and P * H * W < (1 << 31)):
+            return render_f16_views(rgba_layers, homs), None
+        src = _f16_in_place(rgba_layers)
+        h = _up(homs, dev, "homs")
+        out = torch.empty((B, H, W, 3), device=dev, dtype=torch.float32)
+        ckpt = torch.empty((B, (P + 7) // 8, H, W, 4), device=dev, dtype=torch.float32)
+        _call("mpiv_render_train_f16", src, _strides(src), B, H, W, P, h, out, ckpt, _stream(dev))
+        return out, ckpt
     if (B > 1 and rgba_layers.stride(0) == 0 and not broadcast_in_place) or not train_layout_ok(rgba_layers):
         return render(rgba_layers, homs), None
     h = _up(homs, dev, "homs")
@@ -868,6 +912,22 @@ def render_train(rgba_layers: torch.Tensor, homs: torch.Tensor, broadcast_in_pla
     ckpt = torch.empty((B, (P + 7) // 8, H, W, 4), device=dev, dtype=torch.float32)
     _call("mpiv_render_train", rgba_layers, _strides(rgba_layers), B, H, W, P, h, out, ckpt, _stream(dev))
     return out, ckpt
+
+
+def render_f16_views(rgba_layers_f16: torch.Tensor, homs: torch.Tensor) -> torch.Tensor:
+    """Frames [B,H,W,3] of a half MPI [B,H,W,P,4] under homs [B,P,9] through the packed f16 render
+    (render_texel.hip): utils.mpi_render_view_f16's inference body.  One MPI under many views (a stride-0
+    batch) is packed once; a batch of MPIs view by view through one packed buffer."""
+    B, H, W, P, _ = rgba_layers_f16.shape
+    homs = homs.reshape(B, P, 9)
+    if B > 1 and rgba_layers_f16.stride(0) == 0:  # one MPI, many views: pack once
+        return render_packed_f16(pack_planes_f16(rgba_layers_f16[0]), homs, route_float=B >= F16_FLOAT_ONCE_MIN_VIEWS)
+    out = torch.empty((B, H, W, 3), device=rgba_layers_f16.device, dtype=torch.float32)
+    packed = None
+    for b in range(B):
+        packed = pack_planes_f16(rgba_layers_f16[b], out=packed)
+        render_packed_f16(packed, homs[b:b + 1], out=out[b:b + 1], route_float=False)
+    return out
 
 
 # MPIV_BWD_MIN_WS=1: render_backward allocates the smallest workspace (plane groups: config 4
@@ -950,7 +1010,11 @@ def render_backward(rgba_layers: torch.Tensor, homs: torch.Tensor, dout: torch.T
     are made contiguous first), homs [B,P,9] (the forward's), dout [B,H,W,3] ->
     [B,H,W,P,4] contiguous, one gradient per view (a broadcast input's views are summed
     by autograd's expand backward, as in the reference).  Bit-exact to the reference's
-    CPU autograd (render_bwd.hip).  ckpt: render_train()'s checkpoints of the same views
+    CPU autograd (render_bwd.hip).  A float16 rgba_layers (mpiv_render_backward*_f16) is read in place at
+    8 B per texel and its gradient comes back in float16: RN_half of the float route's gradient on
+    rgba_layers.float(), bit for bit, with no float copy of the MPI and no fp32 gradient (other layouts
+    go through a contiguous HALF copy); dhoms are the float route's bits.
+    ckpt: render_train()'s checkpoints of the same views
     (skips recomputing the forward composite).  check (default MPIV_BWD_CHECK): read the
     fallback's abort count back and raise if any view aborted (costs a synchronisation); left at
     None without MPIV_BWD_CHECK, the count is read back asynchronously and a later call raises
@@ -962,11 +1026,12 @@ def render_backward(rgba_layers: torch.Tensor, homs: torch.Tensor, dout: torch.T
     mpiv_render_backward_cam_workspace_size_min bytes."""
     if not want_dmpi and not want_dhoms:
         raise RuntimeError("render_backward: nothing to compute (want_dmpi and want_dhoms are both False)")
-    dev = _dev(rgba_layers, dout)
+    dev = _dev(rgba_layers, dout, f16_first=True)
     B, H, W, P, _ = rgba_layers.shape
     if tuple(dout.shape) != (B, H, W, 3):
         raise RuntimeError(f"grad_output must be [{B},{H},{W},3], got {tuple(dout.shape)}")
-    src = rgba_layers if bwd_layout_ok(rgba_layers) else rgba_layers.contiguous()
+    src = _f16_in_place(rgba_layers) if _f16(rgba_layers) else (
+        rgba_layers if bwd_layout_ok(rgba_layers) else rgba_layers.contiguous())
     L = load()
     # a caller's workspace of at least the minimum (plane groups, render_bwd.hip); our own: the
     # one-group size (the fastest schedule) unless MPIV_BWD_MIN_WS=1
@@ -975,7 +1040,8 @@ def render_backward(rgba_layers: torch.Tensor, homs: torch.Tensor, dout: torch.T
                                                              device=dev)
     if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need or ws.device != dev:
         raise RuntimeError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on {dev}")
-    grad = torch.empty((B, H, W, P, 4), device=dev, dtype=torch.float32) if want_dmpi else None
+    sfx = "_f16" if _f16(rgba_layers) else ""
+    grad = torch.empty((B, H, W, P, 4), device=dev, dtype=rgba_layers.dtype) if want_dmpi else None
     h = _up(homs.reshape(B, P, 9), dev, "homs")
     dout = dout.contiguous()
     if ckpt is not None and (tuple(ckpt.shape) != (B, (P + 7) // 8, H, W, 4) or not ckpt.is_contiguous()
@@ -992,11 +1058,11 @@ def render_backward(rgba_layers: torch.Tensor, homs: torch.Tensor, dout: torch.T
     dhoms = None
     if want_dhoms:
         dhoms = torch.empty((B, P, 9), device=dev, dtype=torch.float32)
-        _call("mpiv_render_backward_cam", src, _strides(src), B, H, W, P, h, dout, ckpt, grad, dhoms, ws, ws.numel(),
-              1 if watch else 0, _stream(dev))
+        _call("mpiv_render_backward_cam" + sfx, src, _strides(src), B, H, W, P, h, dout, ckpt, grad, dhoms, ws,
+              ws.numel(), 1 if watch else 0, _stream(dev))
     else:
-        _call("mpiv_render_backward_watched" if watch else "mpiv_render_backward", src, _strides(src), B, H, W, P, h,
-              dout, ckpt, grad, ws, ws.numel(), _stream(dev))
+        _call(("mpiv_render_backward_watched" if watch else "mpiv_render_backward") + sfx, src, _strides(src), B, H, W,
+              P, h, dout, ckpt, grad, ws, ws.numel(), _stream(dev))
     if BWD_CHECK if check is None else check:
         n = render_backward_status(ws, H, W, P)
         if n:
@@ -1005,22 +1071,31 @@ def render_backward(rgba_layers: torch.Tensor, homs: torch.Tensor, dout: torch.T
     return (grad, dhoms) if want_dhoms else grad
 
 
+def _render_forward(ctx, rgba_layers, homs, in_place: bool):
+    """The forward of RenderFunction / RenderF16Function.  in_place: read a stride-0 broadcast batch in place
+    too, so that every view has its checkpoints."""
+    ctx.homs = homs.detach()
+    ctx.homs_shape = tuple(homs.shape)
+    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:  # keep the composite checkpoints for the backward
+        out, ckpt = render_train(rgba_layers, ctx.homs, broadcast_in_place=in_place)
+        ctx.save_for_backward(rgba_layers, ckpt)
+        return out
+    ctx.save_for_backward(rgba_layers, None)
+    return render(rgba_layers, ctx.homs)
+
+
 class RenderFunction(torch.autograd.Function):
     """Autograd node of the fused render: forward = render(), backward = render_backward() w.r.t.
     rgba_layers and, when the homographies require grad (a device tensor at the end of
-    _host.render_homographies_autograd's chain from tgt_pose, planes and intrinsics), w.r.t. them."""
+    _host.render_homographies_autograd's chain from tgt_pose, planes and intrinsics), w.r.t. them.
+    Float MPIs only: render_train() and render_backward() also serve half tensors, so the refusal of
+    anything but fp32 (mpi_render_view_torch's, as in the reference) is made here."""
 
     @staticmethod
     def forward(ctx, rgba_layers, homs):
-        ctx.homs = homs.detach()
-        ctx.homs_shape = tuple(homs.shape)
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:  # keep the composite checkpoints for the backward
-            # (a camera gradient reads a stride-0 broadcast MPI in place: every view has its checkpoints)
-            out, ckpt = render_train(rgba_layers, ctx.homs, broadcast_in_place=ctx.needs_input_grad[1])
-            ctx.save_for_backward(rgba_layers, ckpt)
-            return out
-        ctx.save_for_backward(rgba_layers, None)
-        return render(rgba_layers, ctx.homs)
+        _dev(rgba_layers)  # raises for a non-fp32 MPI
+        # (a camera gradient reads a stride-0 broadcast MPI in place: every view has its checkpoints)
+        return _render_forward(ctx, rgba_layers, homs, in_place=ctx.needs_input_grad[1])
 
     @staticmethod
     @once_differentiable
@@ -1032,6 +1107,21 @@ class RenderFunction(torch.autograd.Function):
             return grad, dhoms.reshape(ctx.homs_shape)
         grad = render_backward(rgba_layers, ctx.homs, dout, ckpt=ckpt) if ctx.needs_input_grad[0] else None
         return grad, None
+
+
+class RenderF16Function(RenderFunction):
+    """RenderFunction for a half MPI (utils.mpi_render_view_f16 when something requires grad), the only
+    node that admits one: the half tensor is read in place by render_train() (fp32 frame, bit-identical to
+    the float route on rgba_layers.float()) and by the inherited backward, whose render_backward() returns a
+    HALF gradient w.r.t. rgba_layers -- RN_half of the float route's, bit for bit -- and the float route's
+    own bits w.r.t. the homographies.  No fp32 gradient exists at any point, and no float copy of the MPI
+    except for a degenerate frame (H or W < 2: render_train widens its one row or column for the frame)."""
+
+    @staticmethod
+    def forward(ctx, rgba_layers, homs):
+        if not _f16(rgba_layers):
+            raise RuntimeError(f"expected scalar type Half but found {rgba_layers.dtype}")
+        return _render_forward(ctx, rgba_layers, homs, in_place=True)
 
 
 # ---------------------------------------------------------------------------

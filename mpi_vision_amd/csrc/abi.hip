@@ -309,6 +309,48 @@ int launch_chunk(int R, const float* mpi, int64_t vstride, const RenderGeom& g, 
     return launched(nm);
 }
 
+// The training forward of a half view: the 8 x 16 strips, narrow or wide -- the only half instantiations
+// of the forward (launch_chunk's other kernels and its A/B options are the float view's).
+int launch_strip_f16(const uint16_t* mpi, int64_t vstride, const RenderGeom& g, const ChunkGeom& cg, int B,
+                     const float* homs, float* out, float4* ck, size_t lds, hipStream_t q, const char* nm, bool wide) {
+    const int64_t ns = (int64_t)blocks(g.W, kStripTX) * blocks(g.H, 16) * B;
+    if (ns > kMaxGridX) return fail(MPIV_ERR_ARG, "%s: too many blocks", nm);
+    if (g_route) return note_route(ns, 256, "render_chunk_strip_kernel<16, 2, %s, InF16>", wide ? "true" : "false");
+    if (wide)
+        render_chunk_strip_kernel<16, 2, true, InF16><<<(unsigned)ns, 256, lds, q>>>(mpi, vstride, g, cg, B, homs, out, ck);
+    else
+        render_chunk_strip_kernel<16, 2, false, InF16><<<(unsigned)ns, 256, lds, q>>>(mpi, vstride, g, cg, B, homs, out, ck);
+    return launched(nm);
+}
+
+// mpiv_render_train / mpiv_render_train_f16: one schedule, by the texel type.  Strides in Scalars (a texel
+// is 4 of them); a view is narrow while every tap's byte offset stays below the buffer unit's out-of-range
+// offset (2 GiB), so a half view stays narrow up to twice the float texel count.
+template <class TX>
+int render_train_impl(const char* nm, const typename TX::Scalar* mpi, const int64_t st[5], int B, int H, int W, int P,
+                      const float* homs, float* out, float* ckpt, void* stream) {
+    if (!mpi || !st || !homs || !out || !ckpt) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (B <= 0 || H < 2 || W < 2 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape (H, W >= 2)", nm);
+    constexpr int64_t SB = TX::kBytes / 4;  // bytes per Scalar
+    const int64_t rec = ((int64_t)(H - 1) * st[1] + (int64_t)(W - 1) * st[2]) * SB + 8 * TX::kBytes;
+    const size_t ch_lds = (size_t)4 * kWave * 9 * 16 + (size_t)P * 36;
+    if (st[4] != 1 || st[3] != 4 || st[0] % 4 || st[1] % 4 || st[2] % 4 || st[1] < 0 || st[2] < 0 ||
+        (reinterpret_cast<uintptr_t>(mpi) & (TX::kBytes - 1)) || !aligned16(ckpt) || st[1] / 4 >= (1 << 22) ||
+        st[2] / 4 >= (1 << 22) || ch_lds > (size_t)kChunkMaxLds)
+        return fail(MPIV_ERR_ARG, "%s: rgba_layers must be read in place (%d-byte texels, planes contiguous per "
+                    "pixel, row and pixel strides below 2^22 texels, P <= 796)", nm, TX::kBytes);
+    if (view_too_large(H, W, P)) return fail(MPIV_ERR_ARG, kViewTooLarge, nm);
+    // a view whose taps reach the buffer unit's out-of-range offset (2 GiB) is read through 64-bit addresses
+    const bool wide = rec >= (int64_t)kOOB || opt(kOptChunkWide) == 1;
+    const ChunkGeom cg{(int)(st[1] / 4), (int)(st[2] / 4), rec < (int64_t)kOOB ? (int)rec : 0};
+    if constexpr (std::is_same<TX, InF32>::value)
+        return launch_chunk<8, 1>(chunk_rows(), mpi, st[0], make_geom(H, W, P), cg, B, homs, out,
+                                  reinterpret_cast<float4*>(ckpt), ch_lds, S(stream), nm, wide);
+    else
+        return launch_strip_f16(mpi, st[0], make_geom(H, W, P), cg, B, homs, out, reinterpret_cast<float4*>(ckpt),
+                                ch_lds, S(stream), nm, wide);
+}
+
 }  // namespace
 
 extern "C" {
@@ -393,22 +435,12 @@ int mpiv_render(const float* mpi, const int64_t st[5], int B, int H, int W, int 
 
 int mpiv_render_train(const float* mpi, const int64_t st[5], int B, int H, int W, int P, const float* homs,
                       float* out, float* ckpt, void* stream) {
-    const char* nm = "mpiv_render_train";
-    if (!mpi || !st || !homs || !out || !ckpt) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
-    if (B <= 0 || H < 2 || W < 2 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape (H, W >= 2)", nm);
-    const int64_t rec = ((int64_t)(H - 1) * st[1] + (int64_t)(W - 1) * st[2]) * 4 + 8 * 16;
-    const size_t ch_lds = (size_t)4 * kWave * 9 * 16 + (size_t)P * 36;
-    if (st[4] != 1 || st[3] != 4 || st[0] % 4 || st[1] % 4 || st[2] % 4 || st[1] < 0 || st[2] < 0 ||
-        !aligned16(mpi) || !aligned16(ckpt) || st[1] / 4 >= (1 << 22) || st[2] / 4 >= (1 << 22) ||
-        ch_lds > (size_t)kChunkMaxLds)
-        return fail(MPIV_ERR_ARG, "%s: rgba_layers must be read in place (16-byte texels, planes contiguous per "
-                    "pixel, row and pixel strides below 2^22 texels, P <= 796)", nm);
-    if (view_too_large(H, W, P)) return fail(MPIV_ERR_ARG, kViewTooLarge, nm);
-    // a view whose taps reach the buffer unit's out-of-range offset (2 GiB) is read through 64-bit addresses
-    const bool wide = rec >= (int64_t)kOOB || opt(kOptChunkWide) == 1;
-    const ChunkGeom cg{(int)(st[1] / 4), (int)(st[2] / 4), rec < (int64_t)kOOB ? (int)rec : 0};
-    return launch_chunk<8, 1>(chunk_rows(), mpi, st[0], make_geom(H, W, P), cg, B, homs, out,
-                              reinterpret_cast<float4*>(ckpt), ch_lds, S(stream), nm, wide);
+    return render_train_impl<InF32>("mpiv_render_train", mpi, st, B, H, W, P, homs, out, ckpt, stream);
+}
+
+int mpiv_render_train_f16(const uint16_t* mpi, const int64_t st[5], int B, int H, int W, int P, const float* homs,
+                          float* out, float* ckpt, void* stream) {
+    return render_train_impl<InF16>("mpiv_render_train_f16", mpi, st, B, H, W, P, homs, out, ckpt, stream);
 }
 
 int mpiv_pack_planes(const float* mpi, const int64_t st[4], int H, int W, int P, float* packed, void* stream) {
@@ -958,16 +990,28 @@ static size_t cam_extra_bytes(int H, int W, int P) {
     return align256((size_t)P * ntiles * 36) + align256((size_t)H * W * 16);
 }
 
-static int render_backward_impl(const char* nm, const float* mpi, const int64_t st[5], int V, int H, int W, int P,
-                                const float* homs, const float* dout, const float* ckpt, float* dmpi, void* workspace,
-                                size_t ws_bytes, void* stream, bool watched, const CamOut* cam = nullptr) {
+// TX: the texel type of rgba_layers and of its gradient (render_chunk.hip InF32 / InF16): one schedule for
+// the float and the half entries.  Strides in Scalars; checkpoints, d samples and the workspace are fp32
+// either way, so the workspace sizes are the float entries'.  A half view takes the strip kernels wherever
+// the fast recipe runs (its only instantiations) and the production gather and fallbacks.
+extern "C++" {
+template <class TX>
+static int render_backward_impl(const char* nm, const typename TX::Scalar* mpi, const int64_t st[5], int V, int H, int W,
+                                int P, const float* homs, const float* dout, const float* ckpt,
+                                typename TX::Scalar* dmpi, void* workspace, size_t ws_bytes, void* stream, bool watched,
+                                const CamOut* cam = nullptr) {
+    typedef typename TX::Scalar Scalar;
+    typedef typename TX::Grad DT;
+    constexpr bool kHalf = !std::is_same<TX, InF32>::value;
+    constexpr int64_t SB = TX::kBytes / 4;  // bytes per Scalar
     if (!mpi || !st || !homs || !dout || (!dmpi && !cam) || !workspace) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
     if (V <= 0 || H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
-    // in place: planes contiguous per pixel (16-B texels), every tap below the buffer range
-    const int64_t rec = ((int64_t)(H - 1) * st[1] + (int64_t)(W - 1) * st[2]) * 4 + kBwdCH * 16;
-    if (st[4] != 1 || st[3] != 4 || st[0] % 4 || st[1] % 4 || st[2] % 4 || !aligned16(mpi))
-        return fail(MPIV_ERR_ARG, "%s: rgba_layers must have 16-byte aligned texels with planes contiguous per pixel "
-                    "(strides[3] == 4, strides[4] == 1)", nm);
+    // in place: planes contiguous per pixel (16-B texels, 8-B for half), every tap below the buffer range
+    const int64_t rec = ((int64_t)(H - 1) * st[1] + (int64_t)(W - 1) * st[2]) * SB + kBwdCH * TX::kBytes;
+    if (st[4] != 1 || st[3] != 4 || st[0] % 4 || st[1] % 4 || st[2] % 4 ||
+        (reinterpret_cast<uintptr_t>(mpi) & (TX::kBytes - 1)))
+        return fail(MPIV_ERR_ARG, "%s: rgba_layers must have %d-byte aligned texels with planes contiguous per pixel "
+                    "(strides[3] == 4, strides[4] == 1)", nm, TX::kBytes);
     if (st[1] < 0 || st[2] < 0 || st[1] / 4 >= (1 << 22) || st[2] / 4 >= (1 << 22))
         return fail(MPIV_ERR_ARG, "%s: rgba_layers' row and pixel strides must be non-negative and below 2^22 texels", nm);
     // a view whose taps reach the buffer unit's out-of-range offset (2 GiB) is read through 64-bit addresses
@@ -979,8 +1023,8 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     const size_t chain_lds = slots_lds + (h_lds ? (size_t)P * 36 : 0);
     if (ckpt && (!aligned16(ckpt) || H < 2 || W < 2))
         return fail(MPIV_ERR_ARG, "%s: checkpoints must be 16-byte aligned (and come from mpiv_render_train)", nm);
-    if (!aligned16(dmpi) || (reinterpret_cast<uintptr_t>(workspace) & 255))
-        return fail(MPIV_ERR_ARG, "%s: d rgba_layers must be 16-byte and workspace 256-byte aligned", nm);
+    if ((reinterpret_cast<uintptr_t>(dmpi) & (TX::kBytes - 1)) || (reinterpret_cast<uintptr_t>(workspace) & 255))
+        return fail(MPIV_ERR_ARG, "%s: d rgba_layers must be %d-byte and workspace 256-byte aligned", nm, TX::kBytes);
     // pixel ids, bucket ids and order keys are 32-bit
     if (view_too_large(H, W, P)) return fail(MPIV_ERR_ARG, kViewTooLarge, nm);
     // plane groups: one (every plane's d samples resident) when the workspace holds it, else
@@ -1013,6 +1057,9 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     const int64_t ntiles = (int64_t)tiles_x * blocks(H, kGTY);
     const int64_t gather_blocks = ntiles * blocks(P, kGPl);
     if (gather_blocks > kMaxGridX) return fail(MPIV_ERR_ARG, "%s: too many blocks", nm);
+    if (kHalf && opt(kOptBwdGather) != 0)
+        return fail(MPIV_ERR_ARG, "%s: the A/B gather variants (bwd_gather=%d) write fp32 gradients only", nm,
+                    opt(kOptBwdGather));
     if (opt(kOptBwdGather) != 0 && !(MPIV_AB && MPIV_GTR == 1))
         return fail(MPIV_ERR_ARG, "%s: bwd_gather=%d needs an A/B build with one texel row per wave (-DMPIV_GTR=1)", nm,
                     opt(kOptBwdGather));
@@ -1020,6 +1067,13 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     const float margin = (float)opt(kOptBwdMargin) / 64.0f;
     hipStream_t q = S(stream);
     if (g_route) {  // dry run: the chain kernel of this view (production options)
+        if (kHalf) {
+            if (!fast)
+                return note_route((int64_t)blocks(W, kTileX) * blocks(H, kTileY), 256,
+                                  "bwd_chain_kernel<0, false, 1, %s, InF16>", wide ? "true" : "false");
+            return note_route((int64_t)blocks(W, kStripTX) * blocks(H, 8), 256, "bwd_chain_strip_kernel<8, %s, InF16>",
+                              wide ? "true" : "false");
+        }
         if (!fast)
             return note_route((int64_t)blocks(W, kTileX) * blocks(H, kTileY), 256,
                               wide ? "bwd_chain_kernel<0, false, 1, true>" : "bwd_chain_kernel<0, false, 1>");
@@ -1038,9 +1092,9 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     if (fbb == 0) {
         int ncu = 0, pc_t = 0, pc_f = 0;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_t, (const void*)bwd_fallback_kernel<true>, 256, 0) !=
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_t, (const void*)bwd_fallback_kernel<true, DT>, 256, 0) !=
                 hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_f, (const void*)bwd_fallback_kernel<false>, 256, 0) !=
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc_f, (const void*)bwd_fallback_kernel<false, DT>, 256, 0) !=
                 hipSuccess ||
             ncu <= 0 || pc_t <= 0 || pc_f <= 0)
             return fail(MPIV_ERR_HIP, "%s: device query failed", nm);
@@ -1081,8 +1135,8 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
             for (int v = 0; v < V && ok; ++v) {
                 const float* hv = homs + (int64_t)v * P * 9;
                 const float* dv = dout + (int64_t)v * HW * 3;
-                const float* mv = mpi + (int64_t)v * st[0];
-                float4* gv = reinterpret_cast<float4*>(dmpi) + (int64_t)v * HW * P;
+                const Scalar* mv = mpi + (int64_t)v * st[0];
+                DT* gv = reinterpret_cast<DT*>(dmpi) + (int64_t)v * HW * P;
                 const float4* ckv = ckpt ? reinterpret_cast<const float4*>(ckpt) +
                                                (int64_t)v * ((P + kBwdCH - 1) / kBwdCH) * HW
                                          : nullptr;
@@ -1091,8 +1145,8 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
                 if (!ckv) {  // the checkpoints from a forward pass into the workspace (frame into gbuf, unused)
                     const unsigned fb = blocks(W, kStripTX) * blocks(H, 16);
                     const size_t flds = (size_t)chunk_slot_floats<8, 1>() * 4 + (h_lds ? (size_t)P * 36 : 0);
-                    render_chunk_strip_kernel<16, 2><<<fb, 256, flds, q>>>(mv, 0, g, cg, 1, hv,
-                                                                          reinterpret_cast<float*>(gbuf), ws.ckpt, h_lds);
+                    render_chunk_strip_kernel<16, 2, false, TX><<<fb, 256, flds, q>>>(
+                        mv, 0, g, cg, 1, hv, reinterpret_cast<float*>(gbuf), ws.ckpt, h_lds);
                     ckv = ws.ckpt;
                 }
                 if (!force)  // the planes' inverses computed inside (one launch fewer)
@@ -1104,20 +1158,20 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
                     if (k >= 2) chk(hipStreamWaitEvent(q, ax->done[par], 0));  // window par is free again
                     BwdWs wg = win[par];
                     wg.ds_p0 = p_lo;  // the window holds the group's d samples: planes p_lo .. p_hi-1
-                    bwd_chain_strip_kernel<8><<<blocks(W, kStripTX) * blocks(H, 8), 256, chain_lds, q>>>(
+                    bwd_chain_strip_kernel<8, false, TX><<<blocks(W, kStripTX) * blocks(H, 8), 256, chain_lds, q>>>(
                         mv, g, cg, hv, dv, ckv, wg, h_lds, p_lo / kBwdCH, (p_hi + kBwdCH - 1) / kBwdCH, gbuf);
                     chk(hipEventRecord(ax->chain[par], q));
                     chk(hipStreamWaitEvent(a, ax->chain[par], 0));
                     if (!force)
-                        bwd_gather_kernel<false><<<(unsigned)(ntiles * blocks(p_hi - p_lo, kGPl)), kGThreads, 0, a>>>(
+                        bwd_gather_kernel<false, DT><<<(unsigned)(ntiles * blocks(p_hi - p_lo, kGPl)), kGThreads, 0, a>>>(
                             g, hv, wg, gv, margin, p_lo, p_hi - p_lo);
                     bwd_check_kernel<<<1, kWave, 0, a>>>(wg, force, k >= 2);
-                    bwd_fallback_kernel<true><<<fb_blocks, 256, 0, a>>>(g, hv, wg, gv, poll_limit, tick_limit,
+                    bwd_fallback_kernel<true, DT><<<fb_blocks, 256, 0, a>>>(g, hv, wg, gv, poll_limit, tick_limit,
                                                                         fb_mode == 2, p_lo, p_hi);
                     chk(hipEventRecord(ax->done[par], a));
                 }
                 // an aborted group (never expected) leaves the view's gradient NaN, counted once
-                bwd_poison_kernel<<<256, 256, 0, a>>>(win[0].flag, gv, (int64_t)P * HW, win[1].flag, ws.flag + 4, ws.sink);
+                bwd_poison_kernel<DT><<<256, 256, 0, a>>>(win[0].flag, gv, (int64_t)P * HW, win[1].flag, ws.flag + 4, ws.sink);
                 chk(hipEventRecord(ax->view, a));
             }
             chk(hipStreamWaitEvent(q, ax->view, 0));  // the caller's stream: every launch of this call
@@ -1128,33 +1182,57 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     }
     // the strip forward that writes a view's checkpoints into the workspace (no checkpoints from the
     // caller), and the strip chain over chunks [c_lo, c_hi): narrow or wide instantiation by the view
-    auto forward_ckpt = [&](const float* mv, const float* hv, float* frame) {
+    auto forward_ckpt = [&](const Scalar* mv, const float* hv, float* frame) {
         const unsigned fb = blocks(W, kStripTX) * blocks(H, 16);
         const size_t flds = (size_t)chunk_slot_floats<8, 1>() * 4 + (h_lds ? (size_t)P * 36 : 0);
         if (wide)
-            render_chunk_strip_kernel<16, 2, true><<<fb, 256, flds, q>>>(mv, 0, g, cg, 1, hv, frame, ws.ckpt, h_lds);
+            render_chunk_strip_kernel<16, 2, true, TX><<<fb, 256, flds, q>>>(mv, 0, g, cg, 1, hv, frame, ws.ckpt, h_lds);
         else
-            render_chunk_strip_kernel<16, 2><<<fb, 256, flds, q>>>(mv, 0, g, cg, 1, hv, frame, ws.ckpt, h_lds);
+            render_chunk_strip_kernel<16, 2, false, TX><<<fb, 256, flds, q>>>(mv, 0, g, cg, 1, hv, frame, ws.ckpt, h_lds);
     };
-    auto chain_strip = [&](const float* mv, const float* hv, const float* dv, const float4* ckv, const BwdWs& wg,
+    auto chain_strip = [&](const Scalar* mv, const float* hv, const float* dv, const float4* ckv, const BwdWs& wg,
                            int c_lo, int c_hi) {
         const unsigned nb = blocks(W, kStripTX) * blocks(H, 8);
         if (wide)
-            bwd_chain_strip_kernel<8, true><<<nb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, ckv, wg, h_lds, c_lo, c_hi, gbuf);
+            bwd_chain_strip_kernel<8, true, TX><<<nb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, ckv, wg, h_lds, c_lo, c_hi, gbuf);
         else
-            bwd_chain_strip_kernel<8><<<nb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, ckv, wg, h_lds, c_lo, c_hi, gbuf);
+            bwd_chain_strip_kernel<8, false, TX><<<nb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, ckv, wg, h_lds, c_lo, c_hi, gbuf);
+    };
+    // the chain of a narrow float view under the fast recipe: the strips when the forward left checkpoints,
+    // else the two-pass kernel, or an A/B variant (float-only instantiations: a generic lambda, so that the
+    // half schedule never instantiates it)
+    auto chain_float = [&](const auto* mv, const float* hv, const float* dv, const float4* ck, int R, unsigned cb) {
+#define MPIV_CHAIN(CKB, RR)                                                                                  \
+    bwd_chain_kernel<1, CKB, RR><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, CKB ? ck : nullptr, ws, h_lds)
+#if MPIV_AB  // R rows per wave: measured slower (DESIGN.md §8)
+        if (ck && R == 4) { MPIV_CHAIN(true, 4); return; }
+        if (ck && R == 2) { MPIV_CHAIN(true, 2); return; }
+        if (!ck && R == 4) { MPIV_CHAIN(false, 4); return; }
+        if (!ck && R == 2) { MPIV_CHAIN(false, 2); return; }
+        if (ck && opt(kOptChunkStrip) == 4) {  // A/B: 8 x 16 strips (2.41 vs 2.38 ms, r04j_strips_ab.jsonl)
+            bwd_chain_strip_kernel<16><<<blocks(W, kStripTX) * blocks(H, 16), 256, chain_lds, q>>>(
+                mv, g, cg, hv, dv, ck, ws, h_lds, 0, (P + 7) / 8, gbuf);
+            return;
+        }
+#endif
+        (void)R;
+        if (ck && opt(kOptChunkStrip))  // 8 x 8 strips, vertical tap reuse
+            chain_strip(mv, hv, dv, ck, ws, 0, (P + 7) / 8);
+        else if (ck) MPIV_CHAIN(true, 1);
+        else MPIV_CHAIN(false, 1);
+#undef MPIV_CHAIN
     };
     // the camera gradient of chunks [c_lo, c_hi) from the window's d samples, and a view's final sum
-    auto cam_chunks = [&](const float* mv, const float* hv, const BwdWs& wg, int c_lo, int c_hi) {
+    auto cam_chunks = [&](const Scalar* mv, const float* hv, const BwdWs& wg, int c_lo, int c_hi) {
         const dim3 nb((unsigned)cam->ntiles, (unsigned)(c_hi - c_lo));
         if (!fast && wide)
-            bwd_cam_kernel<0, true><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
+            bwd_cam_kernel<0, true, TX><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
         else if (!fast)
-            bwd_cam_kernel<0, false><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
+            bwd_cam_kernel<0, false, TX><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
         else if (wide)
-            bwd_cam_kernel<1, true><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
+            bwd_cam_kernel<1, true, TX><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
         else
-            bwd_cam_kernel<1, false><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
+            bwd_cam_kernel<1, false, TX><<<nb, 256, 0, q>>>(mv, g, cg, hv, wg, c_lo, cam->partials, cam->ntiles);
     };
     auto cam_sum = [&](int v) {
         bwd_cam_sum_kernel<<<P, 256, 0, q>>>(cam->partials, cam->ntiles, cam->dhoms + (int64_t)v * P * 9);
@@ -1170,14 +1248,14 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
         for (int v = 0; v < V; ++v) {
             const float* hv = homs + (int64_t)v * P * 9;
             const float* dv = dout + (int64_t)v * HW * 3;
-            const float* mv = mpi + (int64_t)v * st[0];
+            const Scalar* mv = mpi + (int64_t)v * st[0];
             const float4* ck = ckpt ? reinterpret_cast<const float4*>(ckpt) + (int64_t)v * n * HW : nullptr;
             if (!fast) {  // H or W < 2: the generic two-pass chain, one group
                 const unsigned cb = blocks(W, kTileX) * blocks(H, kTileY);
                 if (wide)
-                    bwd_chain_kernel<0, false, 1, true><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
+                    bwd_chain_kernel<0, false, 1, true, TX><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
                 else
-                    bwd_chain_kernel<0, false, 1><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
+                    bwd_chain_kernel<0, false, 1, false, TX><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
                 cam_chunks(mv, hv, ws, 0, n);
             } else {
                 if (!ck) {
@@ -1200,8 +1278,8 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
     for (int v = 0; v < V; ++v) {
         const float* hv = homs + (int64_t)v * P * 9;
         const float* dv = dout + (int64_t)v * HW * 3;
-        const float* mv = mpi + (int64_t)v * st[0];
-        float4* gv = reinterpret_cast<float4*>(dmpi) + (int64_t)v * HW * P;
+        const Scalar* mv = mpi + (int64_t)v * st[0];
+        DT* gv = reinterpret_cast<DT*>(dmpi) + (int64_t)v * HW * P;
         const float4* ck = ckpt ? reinterpret_cast<const float4*>(ckpt) + (int64_t)v * ((P + kBwdCH - 1) / kBwdCH) * HW
                                 : nullptr;
         if (G > 1) {  // several plane groups, back to front (fast recipe: H, W >= 2 here, P * H * W > 2^25)
@@ -1220,17 +1298,17 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
                 chain_strip(mv, hv, dv, ckv, wg, p_lo / kBwdCH, (p_hi + kBwdCH - 1) / kBwdCH);
                 if (cam) cam_chunks(mv, hv, wg, p_lo / kBwdCH, (p_hi + kBwdCH - 1) / kBwdCH);
                 if (!force)
-                    bwd_gather_kernel<false><<<(unsigned)(ntiles * blocks(p_hi - p_lo, kGPl)), kGThreads, 0, q>>>(
+                    bwd_gather_kernel<false, DT><<<(unsigned)(ntiles * blocks(p_hi - p_lo, kGPl)), kGThreads, 0, q>>>(
                         g, hv, wg, gv, margin, p_lo, p_hi - p_lo);
                 bwd_check_kernel<<<1, kWave, 0, q>>>(wg, force, grp != G - 1);
                 if (fast)
-                    bwd_fallback_kernel<true><<<fb_blocks, 256, 0, q>>>(g, hv, wg, gv, poll_limit, tick_limit, fb_mode == 2, p_lo,
+                    bwd_fallback_kernel<true, DT><<<fb_blocks, 256, 0, q>>>(g, hv, wg, gv, poll_limit, tick_limit, fb_mode == 2, p_lo,
                                                                         p_hi);
                 else
-                    bwd_fallback_kernel<false><<<fb_blocks, 256, 0, q>>>(g, hv, wg, gv, poll_limit, tick_limit, fb_mode == 2, p_lo,
+                    bwd_fallback_kernel<false, DT><<<fb_blocks, 256, 0, q>>>(g, hv, wg, gv, poll_limit, tick_limit, fb_mode == 2, p_lo,
                                                                          p_hi);
             }
-            bwd_poison_kernel<<<256, 256, 0, q>>>(ws.flag, gv, (int64_t)P * HW, nullptr, nullptr, ws.sink);
+            bwd_poison_kernel<DT><<<256, 256, 0, q>>>(ws.flag, gv, (int64_t)P * HW, nullptr, nullptr, ws.sink);
             if (cam) cam_sum(v);
             continue;
         }
@@ -1241,38 +1319,25 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
                 g, hv, ws.inv, (int)ntiles, tiles_x, margin, ws.box, (double)W / (H - 1), (double)H / (W - 1), ws,
                 v == 0 ? 2 : 1);
         // (a wide view always takes the strip kernels: the only wide instantiations of the fast recipe)
-        if (!ck && fast && ((R == 1 && opt(kOptChunkStrip) == 1) || wide)) {
+        // (and so does a half view: the only half instantiations of the fast recipe)
+        if (!ck && fast && ((R == 1 && opt(kOptChunkStrip) == 1) || wide || kHalf)) {
             // no checkpoints: a strip forward pass writes them into the workspace (its frame into
             // this view's d MPI, which the gather / fallback overwrite), then the one-pass chain --
-            // 0.6 + 2.4 ms against 3.0-3.1 for the two-pass chain
-            forward_ckpt(mv, hv, reinterpret_cast<float*>(gv));
+            // 0.6 + 2.4 ms against 3.0-3.1 for the two-pass chain.  The frame is 12 B per pixel: a half
+            // view of one plane (8 B) is too small for it, so there it goes to the d samples' window,
+            // which the chain fills only afterwards.
+            forward_ckpt(mv, hv, (size_t)P * sizeof(DT) >= 12 ? reinterpret_cast<float*>(gv)
+                                                               : reinterpret_cast<float*>(ws.ds));
             ck = ws.ckpt;
         }
-#define MPIV_CHAIN(CKB, RR)                                                                                  \
-    bwd_chain_kernel<1, CKB, RR><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, CKB ? ck : nullptr, ws, h_lds)
         if (!fast && wide)
-            bwd_chain_kernel<0, false, 1, true><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
+            bwd_chain_kernel<0, false, 1, true, TX><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
         else if (!fast)
-            bwd_chain_kernel<0, false, 1><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
-        else if (wide)
+            bwd_chain_kernel<0, false, 1, false, TX><<<cb, 256, chain_lds, q>>>(mv, g, cg, hv, dv, nullptr, ws, h_lds);
+        else if (wide || kHalf)
             chain_strip(mv, hv, dv, ck, ws, 0, (P + 7) / 8);
-#if MPIV_AB  // R rows per wave: measured slower (DESIGN.md §8)
-        else if (ck && R == 4) MPIV_CHAIN(true, 4);
-        else if (ck && R == 2) MPIV_CHAIN(true, 2);
-        else if (!ck && R == 4) MPIV_CHAIN(false, 4);
-        else if (!ck && R == 2) MPIV_CHAIN(false, 2);
-#endif
-#if MPIV_AB
-        else if (ck && opt(kOptChunkStrip) == 4)  // A/B: 8 x 16 strips (2.41 vs 2.38 ms, r04j_strips_ab.jsonl)
-            bwd_chain_strip_kernel<16><<<blocks(W, kStripTX) * blocks(H, 16), 256, chain_lds, q>>>(mv, g, cg, hv, dv, ck,
-                                                                                                ws, h_lds, 0, (P + 7) / 8,
-                                                                                                gbuf);
-#endif
-        else if (ck && opt(kOptChunkStrip))  // 8 x 8 strips, vertical tap reuse
-            chain_strip(mv, hv, dv, ck, ws, 0, (P + 7) / 8);
-        else if (ck) MPIV_CHAIN(true, 1);
-        else MPIV_CHAIN(false, 1);
-#undef MPIV_CHAIN
+        else if constexpr (!kHalf)
+            chain_float(mv, hv, dv, ck, R, cb);
         if (cam) {  // one group: every plane's d samples are resident until the next view's chain
             cam_chunks(mv, hv, ws, 0, (P + kBwdCH - 1) / kBwdCH);
             cam_sum(v);
@@ -1282,24 +1347,25 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
             // its end (+2 % at config 4's 131072 blocks, profiles/r06_bwd_fold.json): small grids only, where
             // the separate launch is what costs
             if (gather_blocks <= kFoldCheckMaxBlocks) {
-                bwd_gather_kernel<true><<<(unsigned)gather_blocks, kGThreads, 0, q>>>(g, hv, ws, gv, margin, 0, P);
+                bwd_gather_kernel<true, DT><<<(unsigned)gather_blocks, kGThreads, 0, q>>>(g, hv, ws, gv, margin, 0, P);
             } else {
-                bwd_gather_kernel<false><<<(unsigned)gather_blocks, kGThreads, 0, q>>>(g, hv, ws, gv, margin, 0, P);
+                bwd_gather_kernel<false, DT><<<(unsigned)gather_blocks, kGThreads, 0, q>>>(g, hv, ws, gv, margin, 0, P);
                 bwd_check_kernel<<<1, kWave, 0, q>>>(ws, 0, 0);
             }
             if (fast)
-                bwd_fallback_kernel<true><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, poll_limit, tick_limit, fb_mode == 2, 0,
+                bwd_fallback_kernel<true, DT><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, poll_limit, tick_limit, fb_mode == 2, 0,
                                                                     P, (int64_t)P * HW);
             else
-                bwd_fallback_kernel<false><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, poll_limit, tick_limit, fb_mode == 2, 0,
+                bwd_fallback_kernel<false, DT><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, poll_limit, tick_limit, fb_mode == 2, 0,
                                                                      P, (int64_t)P * HW);
             continue;
         }
         if (!force) {
 #if MPIV_AB && MPIV_GTR == 1  // one texel row per wave / staging and texel waves: measured slower
+            float4* gvf = reinterpret_cast<float4*>(gv);  // (fp32 gradients only: a half call was refused above)
             if (opt(kOptBwdGather) == 1) {
                 bwd_inverse_kernel<<<blocks(P, 64), 64, 0, q>>>(hv, P, (double)W / (H - 1), (double)H / (W - 1), ws.inv);
-                bwd_gather_wave_kernel<<<(unsigned)gather_blocks, 256, 0, q>>>(g, hv, ws, gv, margin);
+                bwd_gather_wave_kernel<<<(unsigned)gather_blocks, 256, 0, q>>>(g, hv, ws, gvf, margin);
             } else
 #endif
             {
@@ -1308,12 +1374,12 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
                     g, hv, ws.inv, (int)ntiles, tiles_x, margin, ws.box, (double)W / (H - 1), (double)H / (W - 1));
 #if MPIV_AB && MPIV_GTR == 1
                 if (opt(kOptBwdGather) == 2)
-                    bwd_gather_ws_kernel<<<(unsigned)gather_blocks, 2 * kGThreads, 0, q>>>(g, hv, ws, gv, margin);
+                    bwd_gather_ws_kernel<<<(unsigned)gather_blocks, 2 * kGThreads, 0, q>>>(g, hv, ws, gvf, margin);
                 else if (opt(kOptBwdGather) == 3)
-                    bwd_gather_dma_kernel<<<(unsigned)gather_blocks, kGThreads, 0, q>>>(g, hv, ws, gv, margin);
+                    bwd_gather_dma_kernel<<<(unsigned)gather_blocks, kGThreads, 0, q>>>(g, hv, ws, gvf, margin);
                 else
 #endif
-                    bwd_gather_kernel<false><<<(unsigned)gather_blocks, kGThreads, 0, q>>>(g, hv, ws, gv, margin, 0, P);
+                    bwd_gather_kernel<false, DT><<<(unsigned)gather_blocks, kGThreads, 0, q>>>(g, hv, ws, gv, margin, 0, P);
             }
         }
         bwd_check_kernel<<<1, kWave, 0, q>>>(ws, force, 0);
@@ -1323,25 +1389,26 @@ static int render_backward_impl(const char* nm, const float* mpi, const int64_t 
             // keeps its poll-count limit)
         const unsigned bar_polls = poll_limit == ~0u ? (1u << 24) : poll_limit;
         if (fb_mode == 1 && fast)
-            bwd_fallback_barrier_kernel<true><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, bar_polls);
+            bwd_fallback_barrier_kernel<true, DT><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, bar_polls);
         else if (fb_mode == 1)
-            bwd_fallback_barrier_kernel<false><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, bar_polls);
+            bwd_fallback_barrier_kernel<false, DT><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, bar_polls);
         else
 #endif
         if (fast)
-            bwd_fallback_kernel<true><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, poll_limit, tick_limit, fb_mode == 2, 0, P);
+            bwd_fallback_kernel<true, DT><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, poll_limit, tick_limit, fb_mode == 2, 0, P);
         else
-            bwd_fallback_kernel<false><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, poll_limit, tick_limit, fb_mode == 2, 0, P);
+            bwd_fallback_kernel<false, DT><<<fb_blocks, 256, 0, q>>>(g, hv, ws, gv, poll_limit, tick_limit, fb_mode == 2, 0, P);
         // an aborted fallback (never expected) leaves a NaN gradient, never a plausible one
-        bwd_poison_kernel<<<256, 256, 0, q>>>(ws.flag, gv, (int64_t)P * HW, nullptr, nullptr, ws.sink);
+        bwd_poison_kernel<DT><<<256, 256, 0, q>>>(ws.flag, gv, (int64_t)P * HW, nullptr, nullptr, ws.sink);
     }
     return launched(nm);
 }
+}  // extern "C++"
 
 int mpiv_render_backward(const float* mpi, const int64_t st[5], int V, int H, int W, int P, const float* homs,
                          const float* dout, const float* ckpt, float* dmpi, void* workspace, size_t ws_bytes,
                          void* stream) {
-    return render_backward_impl("mpiv_render_backward", mpi, st, V, H, W, P, homs, dout, ckpt, dmpi, workspace, ws_bytes,
+    return render_backward_impl<InF32>("mpiv_render_backward", mpi, st, V, H, W, P, homs, dout, ckpt, dmpi, workspace, ws_bytes,
                                 stream, false);
 }
 
@@ -1349,14 +1416,16 @@ int mpiv_render_backward_watched(const float* mpi, const int64_t st[5], int V, i
                                  const float* dout, const float* ckpt, float* dmpi, void* workspace, size_t ws_bytes,
                                  void* stream) {
     if (!abort_flags_dev()) return fail(MPIV_ERR_HIP, "mpiv_render_backward_watched: no page-locked abort flag");
-    return render_backward_impl("mpiv_render_backward_watched", mpi, st, V, H, W, P, homs, dout, ckpt, dmpi, workspace,
+    return render_backward_impl<InF32>("mpiv_render_backward_watched", mpi, st, V, H, W, P, homs, dout, ckpt, dmpi, workspace,
                                 ws_bytes, stream, true);
 }
 
-int mpiv_render_backward_cam(const float* mpi, const int64_t st[5], int V, int H, int W, int P, const float* homs,
-                             const float* dout, const float* ckpt, float* dmpi, float* dhoms, void* workspace,
-                             size_t ws_bytes, int watched, void* stream) {
-    const char* nm = "mpiv_render_backward_cam";
+extern "C++" {
+template <class TX>
+static int render_backward_cam_impl(const char* nm, const typename TX::Scalar* mpi, const int64_t st[5], int V, int H,
+                                    int W, int P, const float* homs, const float* dout, const float* ckpt,
+                                    typename TX::Scalar* dmpi, float* dhoms, void* workspace, size_t ws_bytes,
+                                    int watched, void* stream) {
     if (!dhoms || !workspace) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
     if (V <= 0 || H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
     if (reinterpret_cast<uintptr_t>(dhoms) & 3) return fail(MPIV_ERR_ARG, "%s: d homographies must be 4-byte aligned", nm);
@@ -1374,8 +1443,40 @@ int mpiv_render_backward_cam(const float* mpi, const int64_t st[5], int V, int H
     cam.ntiles = (int)(blocks(W, kCamTX) * blocks(H, kCamTY));
     cam.partials = reinterpret_cast<float*>(static_cast<char*>(workspace) + base);
     cam.frame = reinterpret_cast<float*>(static_cast<char*>(workspace) + base + align256((size_t)P * cam.ntiles * 36));
-    return render_backward_impl(nm, mpi, st, V, H, W, P, homs, dout, ckpt, dmpi, workspace, base, stream, watched != 0,
+    return render_backward_impl<TX>(nm, mpi, st, V, H, W, P, homs, dout, ckpt, dmpi, workspace, base, stream, watched != 0,
                                 &cam);
+}
+}  // extern "C++"
+
+int mpiv_render_backward_cam(const float* mpi, const int64_t st[5], int V, int H, int W, int P, const float* homs,
+                             const float* dout, const float* ckpt, float* dmpi, float* dhoms, void* workspace,
+                             size_t ws_bytes, int watched, void* stream) {
+    return render_backward_cam_impl<InF32>("mpiv_render_backward_cam", mpi, st, V, H, W, P, homs, dout, ckpt, dmpi, dhoms,
+                                           workspace, ws_bytes, watched, stream);
+}
+
+// The half entries: rgba_layers and its gradient as 8-byte texels of 4 halves (strides in half elements),
+// every other argument, the workspace sizes and the schedule the float entries' (render_backward_impl).
+int mpiv_render_backward_f16(const uint16_t* mpi, const int64_t st[5], int V, int H, int W, int P, const float* homs,
+                             const float* dout, const float* ckpt, uint16_t* dmpi, void* workspace, size_t ws_bytes,
+                             void* stream) {
+    return render_backward_impl<InF16>("mpiv_render_backward_f16", mpi, st, V, H, W, P, homs, dout, ckpt, dmpi, workspace,
+                                       ws_bytes, stream, false);
+}
+
+int mpiv_render_backward_watched_f16(const uint16_t* mpi, const int64_t st[5], int V, int H, int W, int P,
+                                     const float* homs, const float* dout, const float* ckpt, uint16_t* dmpi,
+                                     void* workspace, size_t ws_bytes, void* stream) {
+    if (!abort_flags_dev()) return fail(MPIV_ERR_HIP, "mpiv_render_backward_watched_f16: no page-locked abort flag");
+    return render_backward_impl<InF16>("mpiv_render_backward_watched_f16", mpi, st, V, H, W, P, homs, dout, ckpt, dmpi,
+                                       workspace, ws_bytes, stream, true);
+}
+
+int mpiv_render_backward_cam_f16(const uint16_t* mpi, const int64_t st[5], int V, int H, int W, int P, const float* homs,
+                                 const float* dout, const float* ckpt, uint16_t* dmpi, float* dhoms, void* workspace,
+                                 size_t ws_bytes, int watched, void* stream) {
+    return render_backward_cam_impl<InF16>("mpiv_render_backward_cam_f16", mpi, st, V, H, W, P, homs, dout, ckpt, dmpi,
+                                           dhoms, workspace, ws_bytes, watched, stream);
 }
 
 size_t mpiv_render_backward_cam_workspace_size(int H, int W, int P) {

@@ -58,6 +58,30 @@ __device__ __forceinline__ void bwd_store(float4* p, const float4& v) {
 #ifndef MPIV_BWD_NTOUT
 #define MPIV_BWD_NTOUT 0  // A/B: non-temporal stores of the gather's d MPI only
 #endif
+// One d MPI texel out.  Every production writer of the gradient stores through this helper, by the
+// output texel: a float4 as it is, or (h16x4: the gradient of a half MPI) its four channels rounded to
+// half and written as one 8-byte store.  The rounding is v_cvt_f16_f32 in the default mode: IEEE
+// round-to-nearest-even, overflow to +-inf, half subnormals kept, -0 and NaN preserved -- torch's .half().
+typedef uint2 h16x4;
+template <bool NT = false>
+__device__ __forceinline__ void dmpi_store(float4* p, const float4& v) {
+    if (NT)
+        __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(p));
+    else
+        *p = v;
+}
+template <bool NT = false>
+__device__ __forceinline__ void dmpi_store(h16x4* p, const float4& v) {
+    const unsigned r = __builtin_bit_cast(unsigned short, (_Float16)v.x);
+    const unsigned g = __builtin_bit_cast(unsigned short, (_Float16)v.y);
+    const unsigned b = __builtin_bit_cast(unsigned short, (_Float16)v.z);
+    const unsigned a = __builtin_bit_cast(unsigned short, (_Float16)v.w);
+    const u32x2 w = {r | (g << 16), b | (a << 16)};
+    if (NT)
+        __builtin_nontemporal_store(w, reinterpret_cast<u32x2*>(p));
+    else
+        *reinterpret_cast<u32x2*>(p) = w;
+}
 #ifndef MPIV_GFRAC
 #define MPIV_GFRAC 0  // A/B: the gather stages fractions (2 floats) instead of the 4 corner weights
 #endif
@@ -165,8 +189,9 @@ __device__ __forceinline__ void bwd_pos(const float* h, float fx, float fy, cons
 // columns with the chunk loop outside the row loop (row r+1's north taps come from L1/L2);
 // rows past the frame (nrows < R, wave-uniform) re-sample the last row, uncounted and unstored.
 // WIDE: a view of 2 GiB or more, taps through issue_taps_chunk_wide (a separate instantiation).
-template <int MODE, bool CK, int R, bool WIDE = false>
-__device__ __forceinline__ void bwd_chain_wave(const float* __restrict__ view, const RenderGeom& g,
+// TX: the texel type of the view (render_chunk.hip InF32 / InF16); checkpoints and d samples stay fp32.
+template <int MODE, bool CK, int R, bool WIDE = false, class TX = InF32>
+__device__ __forceinline__ void bwd_chain_wave(const typename TX::Scalar* __restrict__ view, const RenderGeom& g,
                                                const ChunkGeom& cg, const float* __restrict__ hs,
                                                f32x4* __restrict__ slot, int tx0, int y0, int nrows_, int lane,
                                                const float* __restrict__ dout, const float4* __restrict__ ck,
@@ -187,19 +212,19 @@ __device__ __forceinline__ void bwd_chain_wave(const float* __restrict__ view, c
     auto rsrc = [&](int c) { return make_rsrc(view + (int64_t)c * CH * 4, cg.rec_bytes); };
     int ntap = 0;
     // sub-step k of row r, chunk c: pixel tx0 + k*PPS + i, plane c*CH + j (taps counted once)
-    auto issue = [&](int c, int r, int k, const float* hh, ChunkTaps& ts, bool cnt) {
+    auto issue = [&](int c, int r, int k, const float* hh, ChunkTaps<TX>& ts, bool cnt) {
         const int xs = tx0 + k * PPS + i;
         float px, py;
         bwd_pos<MODE>(hh, (float)xs, (float)(y0 + min(r, nrows - 1)), g, px, py);
         int nt;
         if constexpr (WIDE)
-            nt = issue_taps_chunk_wide(view + (int64_t)c * CH * 4, g, cg, j, c * CH + j < g.P, px, py, ts);
+            nt = issue_taps_chunk_wide<TX>(view + (int64_t)c * CH * 4, g, cg, j, c * CH + j < g.P, px, py, ts);
         else
             nt = issue_taps_chunk(rsrc(c), g, cg, j, c * CH + j < g.P, px, py, ts);
         if (cnt && xs < g.W && r < nrows) ntap += nt;
     };
-    auto put = [&](int k, const ChunkTaps& ts) { slot[(k * PPS + i) * (CH + 1) + j] = blend_chunk(ts); };
-    ChunkTaps A, B;
+    auto put = [&](int k, const ChunkTaps<TX>& ts) { slot[(k * PPS + i) * (CH + 1) + j] = blend_chunk(ts); };
+    ChunkTaps<TX> A, B;
     // row r of chunk c into the slot; A holds its sub-step 0 on entry and, on exit, sub-step 0
     // of the next row (r + 1 < R) or of row 0 of chunk cn (issued ahead, cn's homography in h)
     auto sample_row = [&](int c, int r, int cn, bool cnt, bool cnt_next) {
@@ -345,8 +370,8 @@ __device__ __forceinline__ void bwd_chain_wave(const float* __restrict__ view, c
 // Dynamic LDS: 4 per-wave sample slots (64 x (CH+1) float4) + the view's P homographies.
 // MODE 0: generic recipe (H or W < 2); 1: fast recipe, the tile's division proof picks the
 // unguarded path.
-template <int MODE, bool CK, int R, bool WIDE = false>
-__global__ __launch_bounds__(256, R == 1 ? 1 : 4) void bwd_chain_kernel(const float* __restrict__ view, RenderGeom g, ChunkGeom cg,
+template <int MODE, bool CK, int R, bool WIDE = false, class TX = InF32>
+__global__ __launch_bounds__(256, R == 1 ? 1 : 4) void bwd_chain_kernel(const typename TX::Scalar* __restrict__ view, RenderGeom g, ChunkGeom cg,
                                                            const float* __restrict__ homs,
                                                            const float* __restrict__ dout,
                                                            const float4* __restrict__ ck, BwdWs ws, int h_lds) {
@@ -375,11 +400,11 @@ __global__ __launch_bounds__(256, R == 1 ? 1 : 4) void bwd_chain_kernel(const fl
     const int nrows = min(R, g.H - y);
     f32x4* slot = slots + wave * kWave * (kBwdCH + 1);
     if (MODE == 0)
-        bwd_chain_wave<0, CK, R, WIDE>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
+        bwd_chain_wave<0, CK, R, WIDE, TX>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
     else if (proven)
-        bwd_chain_wave<2, CK, R, WIDE>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
+        bwd_chain_wave<2, CK, R, WIDE, TX>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
     else
-        bwd_chain_wave<1, CK, R, WIDE>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
+        bwd_chain_wave<1, CK, R, WIDE, TX>(view, g, cg, hs, slot, tx0, y, nrows, lane, dout, ck, ws);
 }
 
 // The chain fed the forward's checkpoints, as 8 x 8 strips with vertical tap reuse
@@ -392,8 +417,8 @@ __global__ __launch_bounds__(256, R == 1 ? 1 : 4) void bwd_chain_kernel(const fl
 // d samples of one group at a time fit the workspace): g starts from dout for the top group
 // (c_hi == n) and from gbuf otherwise, and leaves in gbuf for the group below (c_lo > 0).
 // WIDE: a view of 2 GiB or more, taps through issue_taps_strip_wide (a separate instantiation).
-template <int MODE, int SR, bool WIDE = false>
-__device__ __forceinline__ void bwd_chain_wave_strip(const float* __restrict__ view, const RenderGeom& g,
+template <int MODE, int SR, bool WIDE = false, class TX = InF32>
+__device__ __forceinline__ void bwd_chain_wave_strip(const typename TX::Scalar* __restrict__ view, const RenderGeom& g,
                                                      const ChunkGeom& cg, const float* __restrict__ hs,
                                                      f32x4* __restrict__ slot, int sx0, int sy0, int lane,
                                                      const float* __restrict__ dout, const float4* __restrict__ ck,
@@ -417,21 +442,21 @@ __device__ __forceinline__ void bwd_chain_wave_strip(const float* __restrict__ v
     };
     int ntap = 0;
     // row k of chunk c: pixel (sx0 + i, sy0 + k), plane c*CH + j (taps counted once)
-    auto issue = [&](int c, int k, const float* hh, int prev_key, bool can_share, StripTaps& t, bool cnt) {
+    auto issue = [&](int c, int k, const float* hh, int prev_key, bool can_share, StripTaps<TX>& t, bool cnt) {
         const int ys = sy0 + k;
         float px, py;
         bwd_pos<MODE>(hh, fx, (float)min(ys, g.H - 1), g, px, py);
         int nt;
         if constexpr (WIDE)
-            nt = issue_taps_strip_wide(view + (int64_t)c * CH * 4, g, cg, j, c * CH + j < g.P, px, py, kstride,
+            nt = issue_taps_strip_wide<TX>(view + (int64_t)c * CH * 4, g, cg, j, c * CH + j < g.P, px, py, kstride,
                                        prev_key, can_share, t);
         else
             nt = issue_taps_strip(make_rsrc(view + (int64_t)c * CH * 4, cg.rec_bytes), g, cg, j, c * CH + j < g.P,
                                   px, py, kstride, prev_key, can_share, t);
         if (cnt && col_in && ys < g.H) ntap += nt;
     };
-    StripTaps A, B;
-    f32x4 sc = {0.f, 0.f, 0.f, 0.f}, sd = sc;
+    StripTaps<TX> A, B;
+    typename TX::Tap sc = TX::zero(), sd = sc;
     // rows 8*hh .. 8*hh+7 of chunk c into the slot; A holds row 8*hh on entry and, on exit, the
     // next row: 8*hh + 8 of chunk c, or row 0 of chunk cn
     auto sample_half = [&](int c, int hh, int cn, bool cnt_next) {
@@ -547,8 +572,8 @@ __device__ __forceinline__ void bwd_chain_wave_strip(const float* __restrict__ v
 
 // One block = 4 waves = a 32 x SR output tile (wave w: the 8 x SR strip at column 8w); LDS and
 // h_lds as bwd_chain_kernel.  Fast recipe only (MODE 1 / 2 by the tile's division proof).
-template <int SR, bool WIDE = false>
-__global__ __launch_bounds__(256, 1) void bwd_chain_strip_kernel(const float* __restrict__ view, RenderGeom g,
+template <int SR, bool WIDE = false, class TX = InF32>
+__global__ __launch_bounds__(256, 1) void bwd_chain_strip_kernel(const typename TX::Scalar* __restrict__ view, RenderGeom g,
                                                                  ChunkGeom cg, const float* __restrict__ homs,
                                                                  const float* __restrict__ dout,
                                                                  const float4* __restrict__ ck, BwdWs ws, int h_lds,
@@ -600,9 +625,9 @@ __global__ __launch_bounds__(256, 1) void bwd_chain_strip_kernel(const float* __
     }
     f32x4* slot = slots + wave * kWave * (kBwdCH + 1);
     if (proven)
-        bwd_chain_wave_strip<2, SR, WIDE>(view, g, cg, hs, slot, sx0, ty0, lane, dout, ck, ws, c_lo, c_hi, gbuf);
+        bwd_chain_wave_strip<2, SR, WIDE, TX>(view, g, cg, hs, slot, sx0, ty0, lane, dout, ck, ws, c_lo, c_hi, gbuf);
     else
-        bwd_chain_wave_strip<1, SR, WIDE>(view, g, cg, hs, slot, sx0, ty0, lane, dout, ck, ws, c_lo, c_hi, gbuf);
+        bwd_chain_wave_strip<1, SR, WIDE, TX>(view, g, cg, hs, slot, sx0, ty0, lane, dout, ck, ws, c_lo, c_hi, gbuf);
 }
 
 // ---- 2. gather: per-texel sums in the reference's order ------------------------------
@@ -1038,9 +1063,10 @@ __device__ __forceinline__ bool last_block_in(int* ctr, int* s_flag) {
 
 // CHECK (round 6, the single-group schedule): the pair-count check (bwd_check_kernel's) runs in
 // the last gather block to finish instead of a launch of its own.
-template <bool CHECK = false>
+// DT: the gradient's texel (float4, or h16x4 for a half MPI: dmpi_store).
+template <bool CHECK = false, class DT = float4>
 __global__ __launch_bounds__(kGThreads, MPIV_GLB) void bwd_gather_kernel(RenderGeom g, const float* __restrict__ homs, BwdWs ws,
-                                                         float4* __restrict__ dmpi, float margin, int p_lo, int np) {
+                                                         DT* __restrict__ dmpi, float margin, int p_lo, int np) {
     __shared__ int s_code[kGCap];                    // local nw-tap bucket of the staged pixel, -1 = none
     __shared__ float s_w[(MPIV_GFRAC ? 2 : 4) * kGWP];  // its bilinear weights, corner-major (kGWP), or
                                                         // (MPIV_GFRAC) its fractions; [kGCap] = 0
@@ -1194,17 +1220,13 @@ __global__ __launch_bounds__(kGThreads, MPIV_GLB) void bwd_gather_kernel(RenderG
     if ((threadIdx.x & (kWave - 1)) == 0 && tot) atomicAdd(&ws.found[blockIdx.x % kCtrSlots], tot);
 #pragma unroll
     for (int r = 0; r < kGTR; ++r) {
-        if (tin[r]) {  // the texel's kGPl planes: one 16*kGPl-B run
-            float4* o = dmpi + ((int64_t)ty[r] * g.W + tx) * g.P + p0;
+        if (tin[r]) {  // the texel's kGPl planes: one 16*kGPl-B run (half: 8*kGPl)
+            DT* o = dmpi + ((int64_t)ty[r] * g.W + tx) * g.P + p0;
 #pragma unroll
             for (int jj = 0; jj < kGPl; ++jj)
-                if (p0 + jj < p_end) {
-                    if (MPIV_BWD_NTOUT)  // A/B: d MPI past the caches (written once, never re-read here)
-                        __builtin_nontemporal_store(f32x4{acc[r][jj][0], acc[r][jj][1], acc[r][jj][2], acc[r][jj][3]},
-                                                    reinterpret_cast<f32x4*>(o + jj));
-                    else
-                        bwd_store(o + jj, make_float4(acc[r][jj][0], acc[r][jj][1], acc[r][jj][2], acc[r][jj][3]));
-                }
+                if (p0 + jj < p_end)  // (A/B, NT: d MPI past the caches -- written once, never re-read here)
+                    dmpi_store<MPIV_BWD_NTOUT || MPIV_BWD_NT>(
+                        o + jj, make_float4(acc[r][jj][0], acc[r][jj][1], acc[r][jj][2], acc[r][jj][3]));
         }
     }
     if (CHECK && last_block_in(ws.flag + kFlagGatherDone, &s_ovf[0]) && threadIdx.x < kWave)
@@ -1856,9 +1878,9 @@ __device__ __forceinline__ unsigned order_key(int pix, int corner) {
 }
 
 #if MPIV_AB  // the round-3 schedule: phases at grid barriers over resident blocks (bwd_fb_mode=1)
-template <bool FAST>
+template <bool FAST, class DT = float4>
 __global__ __launch_bounds__(256) void bwd_fallback_barrier_kernel(RenderGeom g, const float* __restrict__ homs, BwdWs ws,
-                                                           float4* __restrict__ dmpi, unsigned poll_limit) {
+                                                           DT* __restrict__ dmpi, unsigned poll_limit) {
     __shared__ int s_tmp[kScanBlock];
     __shared__ int s_abort;
     if (ws.flag[0] == 0) return;  // uniform over the grid: the tile gather was complete
@@ -2054,7 +2076,7 @@ __global__ __launch_bounds__(256) void bwd_fallback_barrier_kernel(RenderGeom g,
                 a2 = a2 + w * d.z;
                 a3 = a3 + w * d.w;
             }
-            dmpi[(int64_t)t * g.P + pc0 + pl] = make_float4(a0, a1, a2, a3);
+            dmpi_store(dmpi + (int64_t)t * g.P + pc0 + pl, make_float4(a0, a1, a2, a3));
         }
         if (sync()) return;  // the chunk's arrays are reused by the next one
     }
@@ -2129,9 +2151,9 @@ __device__ __forceinline__ void fallback_done(unsigned* done) {
 
 // One item of the fallback pipeline: virtual block bid (of nblk) of phase ph (0: zero the
 // bucket sizes; 1 + kFbPhases * c + k: step k for plane chunk c)
-template <bool FAST>
+template <bool FAST, class DT>
 __device__ void bwd_fallback_item(const RenderGeom& g, const float* __restrict__ homs, const BwdWs& ws,
-                                  float4* __restrict__ dmpi, int ph, int bid, int nblk, int* s_tmp, int p_lo,
+                                  DT* __restrict__ dmpi, int ph, int bid, int nblk, int* s_tmp, int p_lo,
                                   int p_hi) {
     const int tid = threadIdx.x;
     const int64_t gtid = (int64_t)bid * 256 + tid, gstride = (int64_t)nblk * 256;
@@ -2328,7 +2350,7 @@ __device__ void bwd_fallback_item(const RenderGeom& g, const float* __restrict__
                     a2 = a2 + w * d.z;
                     a3 = a3 + w * d.w;
                 }
-                dmpi[(int64_t)t * g.P + pc0 + pl] = make_float4(a0, a1, a2, a3);
+                dmpi_store(dmpi + (int64_t)t * g.P + pc0 + pl, make_float4(a0, a1, a2, a3));
             }
             return;
     }
@@ -2336,7 +2358,7 @@ __device__ void bwd_fallback_item(const RenderGeom& g, const float* __restrict__
 
 // flag words: [0] run the fallback, [1] next ticket, [2] items done, [3] this view aborted,
 // [4] views aborted in this call (sticky; zeroed by mpiv_render_backward's first memset)
-template <bool FAST>
+template <bool FAST, class DT = float4>
 // fixed != 0 (A/B diagnosis): block b takes items b, b + nblk, ... in order instead of tickets
 // (the grid-barrier schedule: needs every block resident)
 // planes [p_lo, p_hi) (a plane group of mpiv_render_backward, or all of them)
@@ -2344,7 +2366,7 @@ template <bool FAST>
 // view (its poison_n d MPI texels) by the last block to leave, instead of a launch of its own after
 // every view.
 __global__ __launch_bounds__(256) void bwd_fallback_kernel(RenderGeom g, const float* __restrict__ homs,
-                                                                  BwdWs ws, float4* __restrict__ dmpi,
+                                                                  BwdWs ws, DT* __restrict__ dmpi,
                                                                   unsigned poll_limit, unsigned long long tick_limit,
                                                                   int fixed, int p_lo, int p_hi, int64_t poison_n = 0) {
     __shared__ int s_tmp[kScanBlock];
@@ -2371,11 +2393,11 @@ __global__ __launch_bounds__(256) void bwd_fallback_kernel(RenderGeom g, const f
                 __hip_atomic_load(ws.flag + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
                 const float q = __builtin_nanf("");
                 if (tid == 0 && ws.sink) __hip_atomic_store(ws.sink, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                for (int64_t i = tid; i < poison_n; i += 256) dmpi[i] = make_float4(q, q, q, q);
+                for (int64_t i = tid; i < poison_n; i += 256) dmpi_store(dmpi + i, make_float4(q, q, q, q));
             }
             return;
         }
-        bwd_fallback_item<FAST>(g, homs, ws, dmpi, t / nblk, t % nblk, nblk, s_tmp, p_lo, p_hi);
+        bwd_fallback_item<FAST, DT>(g, homs, ws, dmpi, t / nblk, t % nblk, nblk, s_tmp, p_lo, p_hi);
         fallback_done(done);
     }
 }
@@ -2418,7 +2440,8 @@ __global__ __launch_bounds__(256) void ticket_selftest_kernel(unsigned* __restri
 // After the fallback: a view whose pipeline aborted (flag[3], or flag_b[3] of the overlapped
 // schedule's second counter set) gets a NaN gradient; count (non-null: the overlapped schedule,
 // whose fallbacks do not count) adds the view once
-__global__ __launch_bounds__(256) void bwd_poison_kernel(const int* __restrict__ flag, float4* __restrict__ dmpi,
+template <class DT = float4>
+__global__ __launch_bounds__(256) void bwd_poison_kernel(const int* __restrict__ flag, DT* __restrict__ dmpi,
                                                          int64_t n, const int* __restrict__ flag_b = nullptr,
                                                          int* __restrict__ count = nullptr, int* sink = nullptr) {
     if (flag[3] == 0 && (!flag_b || flag_b[3] == 0)) return;
@@ -2426,7 +2449,7 @@ __global__ __launch_bounds__(256) void bwd_poison_kernel(const int* __restrict__
     if (sink && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(sink, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     const float q = __builtin_nanf("");
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        dmpi[i] = make_float4(q, q, q, q);
+        dmpi_store(dmpi + i, make_float4(q, q, q, q));
 }
 
 }  // namespace mpiv

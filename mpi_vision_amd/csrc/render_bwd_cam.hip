@@ -56,8 +56,10 @@ __device__ __forceinline__ bool cam_mid(float a) {
     return m >= 0x1p-60f && m <= 0x1p60f;  // false for NaN
 }
 
-template <int MODE, bool WIDE>
-__global__ __launch_bounds__(256) void bwd_cam_kernel(const float* __restrict__ view, RenderGeom g, ChunkGeom cg,
+// TX: the texel type of the view (render_chunk.hip); a half tap's channels are converted (exactly) where
+// the float kernel reads them, so the sums see the same values in the same order.
+template <int MODE, bool WIDE, class TX = InF32>
+__global__ __launch_bounds__(256) void bwd_cam_kernel(const typename TX::Scalar* __restrict__ view, RenderGeom g, ChunkGeom cg,
                                                       const float* __restrict__ homs, BwdWs ws, int c_lo,
                                                       float* __restrict__ partials, int ntiles) {
     constexpr int CH = kBwdCH;
@@ -95,11 +97,11 @@ __global__ __launch_bounds__(256) void bwd_cam_kernel(const float* __restrict__ 
                     const float fx = (float)min(x, g.W - 1);
                     float px, py;
                     bwd_pos<MODE>(h, fx, fy, g, px, py);
-                    ChunkTaps t;
+                    ChunkTaps<TX> t;
                     int nt;
                     const bool on = live && x < g.W;
                     if constexpr (WIDE)
-                        nt = issue_taps_chunk_wide(view + (int64_t)c * CH * 4, g, cg, j, on, px, py, t);
+                        nt = issue_taps_chunk_wide<TX>(view + (int64_t)c * CH * 4, g, cg, j, on, px, py, t);
                     else
                         nt = issue_taps_chunk(make_rsrc(view + (int64_t)c * CH * 4, cg.rec_bytes), g, cg, j, on, px, py,
                                               t);
@@ -110,9 +112,11 @@ __global__ __launch_bounds__(256) void bwd_cam_kernel(const float* __restrict__ 
                         float gx = 0.0f, gy = 0.0f;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
-                            const float tx = __builtin_fmaf(t.d[q] - t.c[q], n, (t.b[q] - t.a[q]) * s);
+                            const float ta = TX::chan(t.a, q), tb = TX::chan(t.b, q);
+                            const float tc = TX::chan(t.c, q), td = TX::chan(t.d, q);
+                            const float tx = __builtin_fmaf(td - tc, n, (tb - ta) * s);
                             gx = __builtin_fmaf(tx, dsv[q], gx);
-                            const float ty = __builtin_fmaf(t.d[q] - t.b[q], w, (t.c[q] - t.a[q]) * e);
+                            const float ty = __builtin_fmaf(td - tb, w, (tc - ta) * e);
                             gy = __builtin_fmaf(ty, dsv[q], gy);
                         }
                         gx = gx * g.half_w;  // grid_sample's unnormalise multipliers

@@ -47,24 +47,67 @@ struct ChunkGeom {
     int rec_bytes;     // buffer range from a chunk's base: every live tap is below it
 };
 
+// The texel type of the in-place readers: what a tap instruction loads and how a channel of it
+// becomes the float the blend multiplies.  kBytes scales every byte offset (taps, chunk bases, the
+// buffer range); strides and plane offsets stay in texels (ChunkGeom), a texel being 4 Scalars.
+//   InF32  the reference's float texels: a 16-byte load, the channels as they are
+//   InF16  half texels (the MPI a network emits under autocast): ONE 8-byte load of 4 halves per tap,
+//          converted at blend time with one v_cvt_f32_f16 per channel -- exact, subnormals included,
+//          so weights, fma chain and over-operator are the float kernels' own on the same values as
+//          x16.float().  The 8 planes of a chunk are a 64-byte run per pixel instead of 128.
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+__device__ u32x2 llvm_raw_buffer_load_v2i32(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset,
+                                            int aux) __asm("llvm.amdgcn.raw.ptr.buffer.load.v2i32");
+
+struct InF32 {
+    typedef float Scalar;
+    typedef float4 Grad;  // the texel of the gradient w.r.t. such a view (render_bwd.hip dmpi_store)
+    typedef f32x4 Tap;
+    static constexpr int kBytes = 16, kWords = 4;
+    static __device__ __forceinline__ Tap zero() { return Tap{0.f, 0.f, 0.f, 0.f}; }
+    static __device__ __forceinline__ Tap load(__amdgpu_buffer_rsrc_t r, int off) {
+        return llvm_raw_buffer_load_v4f32(r, off, 0, 0);
+    }
+    static __device__ __forceinline__ Tap load_global(const Scalar* p) { return *reinterpret_cast<const f32x4*>(p); }
+    static __device__ __forceinline__ float chan(const Tap& t, int k) { return t[k]; }
+};
+
+struct InF16 {
+    typedef uint16_t Scalar;
+    typedef uint2 Grad;  // 4 halves
+    typedef u32x2 Tap;  // (R | G << 16, B | A << 16)
+    static constexpr int kBytes = 8, kWords = 2;
+    static __device__ __forceinline__ Tap zero() { return Tap{0u, 0u}; }
+    static __device__ __forceinline__ Tap load(__amdgpu_buffer_rsrc_t r, int off) {
+        return llvm_raw_buffer_load_v2i32(r, off, 0, 0);
+    }
+    static __device__ __forceinline__ Tap load_global(const Scalar* p) { return *reinterpret_cast<const u32x2*>(p); }
+    static __device__ __forceinline__ float chan(const Tap& t, int k) {
+        const unsigned w = t[k >> 1];
+        return (float)__builtin_bit_cast(_Float16, (unsigned short)((k & 1) ? (w >> 16) : (w & 0xFFFFu)));
+    }
+};
+
 // One sample in flight: four taps + the fractional offsets; the bilinear weights are
 // formed when the taps are blended (the same products as issue_taps_padded's, so the
 // result is identical) -- two VGPRs fewer per sample in flight.
+template <class TX = InF32>
 struct ChunkTaps {
-    f32x4 a, b, c, d;  // NW, NE, SW, SE
+    typename TX::Tap a, b, c, d;  // NW, NE, SW, SE
     float wx, wy;
 };
 
-__device__ __forceinline__ f32x4 blend_chunk(const ChunkTaps& t) {
+template <class TX>
+__device__ __forceinline__ f32x4 blend_chunk(const ChunkTaps<TX>& t) {
     const float ex = 1.0f - t.wx, sy = 1.0f - t.wy;
     const float nw = sy * ex, ne = sy * t.wx, sw = t.wy * ex, se = t.wy * t.wx;
     f32x4 o;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        float acc = t.a[k] * nw;
-        acc = __builtin_fmaf(t.b[k], ne, acc);
-        acc = __builtin_fmaf(t.c[k], sw, acc);
-        acc = __builtin_fmaf(t.d[k], se, acc);
+        float acc = TX::chan(t.a, k) * nw;
+        acc = __builtin_fmaf(TX::chan(t.b, k), ne, acc);
+        acc = __builtin_fmaf(TX::chan(t.c, k), sw, acc);
+        acc = __builtin_fmaf(TX::chan(t.d, k), se, acc);
         o[k] = acc;
     }
     return o;
@@ -76,8 +119,9 @@ __device__ __forceinline__ f32x4 blend_chunk(const ChunkTaps& t) {
 // tap of a lane past the last plane, gets kOOB: the buffer unit returns 0 without an access.
 // Returns the number of taps inside the image (0 for dead lanes; the backward counts the
 // texel contributions it must find, render_bwd.hip).
+template <class TX>
 __device__ __forceinline__ int issue_taps_chunk(__amdgpu_buffer_rsrc_t r, const RenderGeom& g, const ChunkGeom& cg,
-                                                int jt, bool live, float px, float py, ChunkTaps& t) {
+                                                int jt, bool live, float px, float py, ChunkTaps<TX>& t) {
     const float fx0 = floorf(px), fy0 = floorf(py);
     t.wx = px - fx0;
     t.wy = py - fy0;
@@ -86,12 +130,13 @@ __device__ __forceinline__ int issue_taps_chunk(__amdgpu_buffer_rsrc_t r, const 
     const bool x0 = (unsigned)ix < (unsigned)g.W, x1 = (unsigned)(ix + 1) < (unsigned)g.W;
     const bool y0 = live && (unsigned)iy < (unsigned)g.H, y1 = live && (unsigned)(iy + 1) < (unsigned)g.H;
     // wrapping 32-bit arithmetic: the value is only used where every tap index is valid
-    const int off = (int)(((unsigned)__mul24(iy, cg.row_t) + (unsigned)__mul24(ix, cg.pix_t) + (unsigned)jt) * 16u);
-    const int pb = cg.pix_t * 16, rb = cg.row_t * 16;
-    t.a = llvm_raw_buffer_load_v4f32(r, (x0 && y0) ? off : kOOB, 0, 0);
-    t.b = llvm_raw_buffer_load_v4f32(r, (x1 && y0) ? off + pb : kOOB, 0, 0);
-    t.c = llvm_raw_buffer_load_v4f32(r, (x0 && y1) ? off + rb : kOOB, 0, 0);
-    t.d = llvm_raw_buffer_load_v4f32(r, (x1 && y1) ? off + rb + pb : kOOB, 0, 0);
+    const int off = (int)(((unsigned)__mul24(iy, cg.row_t) + (unsigned)__mul24(ix, cg.pix_t) + (unsigned)jt) *
+                          (unsigned)TX::kBytes);
+    const int pb = cg.pix_t * TX::kBytes, rb = cg.row_t * TX::kBytes;
+    t.a = TX::load(r, (x0 && y0) ? off : kOOB);
+    t.b = TX::load(r, (x1 && y0) ? off + pb : kOOB);
+    t.c = TX::load(r, (x0 && y1) ? off + rb : kOOB);
+    t.d = TX::load(r, (x1 && y1) ? off + rb + pb : kOOB);
     return ((int)x0 + (int)x1) * ((int)y0 + (int)y1);
 }
 
@@ -100,17 +145,20 @@ __device__ __forceinline__ int issue_taps_chunk(__amdgpu_buffer_rsrc_t r, const 
 // no __mul24, no wrap -- and the tap is a 16-byte global load executed only by the lanes whose tap
 // indices passed the image test (and whose plane exists): every other lane keeps +0 and touches no
 // memory, the contract the buffer unit's range check gives the narrow kernels.  A tap inside the
-// image is always loaded, whatever its weight.
-__device__ __forceinline__ f32x4 load_tap_wide(const float* __restrict__ base, int64_t off, bool ok) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (ok) v = *reinterpret_cast<const f32x4*>(base + off);  // the address is formed from checked indices only
+// image is always loaded, whatever its weight.  (A half texel: an 8-byte global load; off in Scalars.)
+template <class TX>
+__device__ __forceinline__ typename TX::Tap load_tap_wide(const typename TX::Scalar* __restrict__ base, int64_t off,
+                                                          bool ok) {
+    typename TX::Tap v = TX::zero();
+    if (ok) v = TX::load_global(base + off);  // the address is formed from checked indices only
     return v;
 }
 
 // issue_taps_chunk for a wide view; base: the chunk's first texel of pixel (0, 0)
-__device__ __forceinline__ int issue_taps_chunk_wide(const float* __restrict__ base, const RenderGeom& g,
+template <class TX>
+__device__ __forceinline__ int issue_taps_chunk_wide(const typename TX::Scalar* __restrict__ base, const RenderGeom& g,
                                                      const ChunkGeom& cg, int jt, bool live, float px, float py,
-                                                     ChunkTaps& t) {
+                                                     ChunkTaps<TX>& t) {
     const float fx0 = floorf(px), fy0 = floorf(py);
     t.wx = px - fx0;
     t.wy = py - fy0;
@@ -118,13 +166,13 @@ __device__ __forceinline__ int issue_taps_chunk_wide(const float* __restrict__ b
     const int iy = (int)__builtin_amdgcn_fmed3f(fy0, -2.0f, (float)g.H);
     const bool x0 = (unsigned)ix < (unsigned)g.W, x1 = (unsigned)(ix + 1) < (unsigned)g.W;
     const bool y0 = live && (unsigned)iy < (unsigned)g.H, y1 = live && (unsigned)(iy + 1) < (unsigned)g.H;
-    // floats from the chunk base to the NW tap: |iy * row_t|, |ix * pix_t| < 2^45, exact in 64 bits
+    // Scalars from the chunk base to the NW tap: |iy * row_t|, |ix * pix_t| < 2^45, exact in 64 bits
     const int64_t off = ((int64_t)iy * cg.row_t + (int64_t)ix * cg.pix_t + jt) * 4;
     const int64_t pf = (int64_t)cg.pix_t * 4, rf = (int64_t)cg.row_t * 4;
-    t.a = load_tap_wide(base, off, x0 && y0);
-    t.b = load_tap_wide(base, off + pf, x1 && y0);
-    t.c = load_tap_wide(base, off + rf, x0 && y1);
-    t.d = load_tap_wide(base, off + rf + pf, x1 && y1);
+    t.a = load_tap_wide<TX>(base, off, x0 && y0);
+    t.b = load_tap_wide<TX>(base, off + pf, x1 && y0);
+    t.c = load_tap_wide<TX>(base, off + rf, x0 && y1);
+    t.d = load_tap_wide<TX>(base, off + rf + pf, x1 && y1);
     return ((int)x0 + (int)x1) * ((int)y0 + (int)y1);
 }
 
@@ -166,7 +214,7 @@ __device__ __forceinline__ void render_chunk_wave(const float* __restrict__ view
         return make_rsrc(view + (int64_t)c * CH * 4, cg.rec_bytes);
     };
     // sub-step k of row r, chunk c: pixel (tx0 + k*PPS + i, row r), plane c*CH + j
-    auto issue = [&](int c, int r, int k, const float* hh, ChunkTaps& ts) {
+    auto issue = [&](int c, int r, int k, const float* hh, ChunkTaps<>& ts) {
         float px, py;
         const float fy = (float)(y0 + min(r, nrows - 1));
         chunk_pos<GUARD>(hh, (float)(tx0 + k * PPS + i), fy, g, px, py);
@@ -174,7 +222,7 @@ __device__ __forceinline__ void render_chunk_wave(const float* __restrict__ view
     };
     constexpr int QP = kWave / SPLIT;  // pixels per composite phase
     constexpr int KP = CH / SPLIT;     // sub-steps per composite phase
-    auto put = [&](int k, const ChunkTaps& ts) { slot[((k * PPS + i) % QP) * (CH + 1) + j] = blend_chunk(ts); };
+    auto put = [&](int k, const ChunkTaps<>& ts) { slot[((k * PPS + i) % QP) * (CH + 1) + j] = blend_chunk(ts); };
     // composite phase h of row r: lane = pixel tx0 + lane (lanes of that phase only), planes
     // c*CH .. c*CH+CH-1 back to front
     auto composite = [&](int c, int hph, int r) {
@@ -201,7 +249,7 @@ __device__ __forceinline__ void render_chunk_wave(const float* __restrict__ view
             }
         }
     };
-    ChunkTaps A, B;
+    ChunkTaps<> A, B;
     load_h(0, h);
     issue(0, 0, 0, h, A);
     for (int c = 0; c < nchunk; ++c) {
@@ -258,12 +306,12 @@ __device__ __forceinline__ void render_chunk_wave_ring(const float* __restrict__
 #pragma unroll
         for (int k = 0; k < 9; ++k) d[k] = hs[p * 9 + k];
     };
-    auto issue = [&](int c, int k, const float* hh, ChunkTaps& ts) {
+    auto issue = [&](int c, int k, const float* hh, ChunkTaps<>& ts) {
         float px, py;
         chunk_pos<GUARD>(hh, (float)(tx0 + k * PPS + i), fy, g, px, py);
         issue_taps_chunk(make_rsrc(view + (int64_t)c * CH * 4, cg.rec_bytes), g, cg, j, c * CH + j < g.P, px, py, ts);
     };
-    auto put = [&](int k, const ChunkTaps& ts) { slot[(k * PPS + i) * (CH + 1) + j] = blend_chunk(ts); };
+    auto put = [&](int k, const ChunkTaps<>& ts) { slot[(k * PPS + i) * (CH + 1) + j] = blend_chunk(ts); };
     auto over_px = [&](const f32x4& s, bool first) {
         const float a = first ? 1.0f : s[3];
         const float om = 1.0f - a;
@@ -271,7 +319,7 @@ __device__ __forceinline__ void render_chunk_wave_ring(const float* __restrict__
         cg_ = over(s[1], a, om, cg_);
         cb = over(s[2], a, om, cb);
     };
-    ChunkTaps T[NT];
+    ChunkTaps<> T[NT];
     load_h(0, hc);
 #pragma unroll
     for (int k = 0; k + 1 < NT; ++k) issue(0, k, hc, T[k]);
@@ -321,8 +369,9 @@ __device__ __forceinline__ void render_chunk_wave_ring(const float* __restrict__
 // render_chunk_wave's; the composite reads the same slot rows (slot row = k*8 + column =
 // the lane of pixel (column, row k)).  Identical arithmetic: shared taps are the same
 // texels' values, so frames and checkpoints are bit-identical to render_chunk_wave's.
+template <class TX = InF32>
 struct StripTaps {
-    f32x4 a, b, c, d;  // NW, NE (own, when some lane of the wave needs them), SW, SE
+    typename TX::Tap a, b, c, d;  // NW, NE (own, when some lane of the wave needs them), SW, SE
     float wx, wy;
     int key;           // clamped tap origin iy * kstride + ix
     bool sh;           // this lane's NW, NE = the previous row's SW, SE
@@ -332,9 +381,10 @@ struct StripTaps {
 // issue_taps_chunk for a strip row: the south taps always, the north taps only where some
 // lane of the wave does not continue the previous row (t.own).  Returns the number of taps
 // inside the image (whether gathered or shared: the backward's pair count).
+template <class TX>
 __device__ __forceinline__ int issue_taps_strip(__amdgpu_buffer_rsrc_t r, const RenderGeom& g, const ChunkGeom& cg,
                                                 int jt, bool live, float px, float py, int kstride, int prev_key,
-                                                bool can_share, StripTaps& t) {
+                                                bool can_share, StripTaps<TX>& t) {
     const float fx0 = floorf(px), fy0 = floorf(py);
     t.wx = px - fx0;
     t.wy = py - fy0;
@@ -342,25 +392,27 @@ __device__ __forceinline__ int issue_taps_strip(__amdgpu_buffer_rsrc_t r, const 
     const int iy = (int)__builtin_amdgcn_fmed3f(fy0, -2.0f, (float)g.H);
     const bool x0 = (unsigned)ix < (unsigned)g.W, x1 = (unsigned)(ix + 1) < (unsigned)g.W;
     const bool y0 = live && (unsigned)iy < (unsigned)g.H, y1 = live && (unsigned)(iy + 1) < (unsigned)g.H;
-    const int off = (int)(((unsigned)__mul24(iy, cg.row_t) + (unsigned)__mul24(ix, cg.pix_t) + (unsigned)jt) * 16u);
-    const int pb = cg.pix_t * 16, rb = cg.row_t * 16;
+    const int off = (int)(((unsigned)__mul24(iy, cg.row_t) + (unsigned)__mul24(ix, cg.pix_t) + (unsigned)jt) *
+                          (unsigned)TX::kBytes);
+    const int pb = cg.pix_t * TX::kBytes, rb = cg.row_t * TX::kBytes;
     t.key = iy * kstride + ix;
     t.sh = can_share && t.key == prev_key + kstride;
-    t.c = llvm_raw_buffer_load_v4f32(r, (x0 && y1) ? off + rb : kOOB, 0, 0);
-    t.d = llvm_raw_buffer_load_v4f32(r, (x1 && y1) ? off + rb + pb : kOOB, 0, 0);
+    t.c = TX::load(r, (x0 && y1) ? off + rb : kOOB);
+    t.d = TX::load(r, (x1 && y1) ? off + rb + pb : kOOB);
     t.own = __builtin_amdgcn_ballot_w64(!t.sh) != 0;
     if (t.own) {  // wave-uniform: some lane needs its own north taps
-        t.a = llvm_raw_buffer_load_v4f32(r, (!t.sh && x0 && y0) ? off : kOOB, 0, 0);
-        t.b = llvm_raw_buffer_load_v4f32(r, (!t.sh && x1 && y0) ? off + pb : kOOB, 0, 0);
+        t.a = TX::load(r, (!t.sh && x0 && y0) ? off : kOOB);
+        t.b = TX::load(r, (!t.sh && x1 && y0) ? off + pb : kOOB);
     }
     return ((int)x0 + (int)x1) * ((int)y0 + (int)y1);
 }
 
 // issue_taps_strip for a wide view (issue_taps_chunk_wide's addressing and loads; the same keys,
 // sharing and count)
-__device__ __forceinline__ int issue_taps_strip_wide(const float* __restrict__ base, const RenderGeom& g,
+template <class TX>
+__device__ __forceinline__ int issue_taps_strip_wide(const typename TX::Scalar* __restrict__ base, const RenderGeom& g,
                                                      const ChunkGeom& cg, int jt, bool live, float px, float py,
-                                                     int kstride, int prev_key, bool can_share, StripTaps& t) {
+                                                     int kstride, int prev_key, bool can_share, StripTaps<TX>& t) {
     const float fx0 = floorf(px), fy0 = floorf(py);
     t.wx = px - fx0;
     t.wy = py - fy0;
@@ -372,19 +424,21 @@ __device__ __forceinline__ int issue_taps_strip_wide(const float* __restrict__ b
     const int64_t pf = (int64_t)cg.pix_t * 4, rf = (int64_t)cg.row_t * 4;
     t.key = iy * kstride + ix;
     t.sh = can_share && t.key == prev_key + kstride;
-    t.c = load_tap_wide(base, off + rf, x0 && y1);
-    t.d = load_tap_wide(base, off + rf + pf, x1 && y1);
+    t.c = load_tap_wide<TX>(base, off + rf, x0 && y1);
+    t.d = load_tap_wide<TX>(base, off + rf + pf, x1 && y1);
     t.own = __builtin_amdgcn_ballot_w64(!t.sh) != 0;
     if (t.own) {  // wave-uniform: some lane needs its own north taps
-        t.a = load_tap_wide(base, off, !t.sh && x0 && y0);
-        t.b = load_tap_wide(base, off + pf, !t.sh && x1 && y0);
+        t.a = load_tap_wide<TX>(base, off, !t.sh && x0 && y0);
+        t.b = load_tap_wide<TX>(base, off + pf, !t.sh && x1 && y0);
     }
     return ((int)x0 + (int)x1) * ((int)y0 + (int)y1);
 }
 
 // the blended sample of a strip row; pc, pd: the previous row's south taps of this lane
-__device__ __forceinline__ f32x4 blend_strip(const StripTaps& t, const f32x4& pc, const f32x4& pd) {
-    ChunkTaps u;
+template <class TX>
+__device__ __forceinline__ f32x4 blend_strip(const StripTaps<TX>& t, const typename TX::Tap& pc,
+                                             const typename TX::Tap& pd) {
+    ChunkTaps<TX> u;
     u.a = pc;  // every lane continues (the common case): no per-lane select
     u.b = pd;
     u.c = t.c;
@@ -394,7 +448,7 @@ __device__ __forceinline__ f32x4 blend_strip(const StripTaps& t, const f32x4& pc
     if (t.own) {
         asm volatile("");  // keeps this a real (wave-uniform) branch
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < TX::kWords; ++q) {
             u.a[q] = t.sh ? pc[q] : t.a[q];
             u.b[q] = t.sh ? pd[q] : t.b[q];
         }
@@ -405,8 +459,9 @@ __device__ __forceinline__ f32x4 blend_strip(const StripTaps& t, const f32x4& pc
 // SR strip rows (8 or 16: a chunk's sub-steps, one composite phase per 8 rows) and a ring of
 // NT rows in flight (row k + NT - 1 issued while row k blends, running on into the next chunk).
 // WIDE: the taps through issue_taps_strip_wide (a separate instantiation: the narrow one is unchanged).
-template <bool GUARD, int SR, int NT, bool WIDE = false>
-__device__ __forceinline__ void render_chunk_wave_strip(const float* __restrict__ view, const RenderGeom& g,
+// TX: the texel type (InF32, or InF16 for a half MPI read in place; the checkpoints stay fp32).
+template <bool GUARD, int SR, int NT, bool WIDE = false, class TX = InF32>
+__device__ __forceinline__ void render_chunk_wave_strip(const typename TX::Scalar* __restrict__ view, const RenderGeom& g,
                                                         const ChunkGeom& cg, const float* __restrict__ hs,
                                                         f32x4* __restrict__ slot, int sx0, int sy0, int lane,
                                                         float (&cr)[SR / 8], float (&cg_)[SR / 8], float (&cb)[SR / 8],
@@ -424,18 +479,18 @@ __device__ __forceinline__ void render_chunk_wave_strip(const float* __restrict_
         for (int k = 0; k < 9; ++k) d[k] = hs[p * 9 + k];
     };
     // row k of chunk c: pixel (sx0 + i, sy0 + k), plane c*CH + j (issue_taps_chunk's taps)
-    auto issue = [&](int c, int k, const float* hh, int prev_key, bool can_share, StripTaps& t) {
+    auto issue = [&](int c, int k, const float* hh, int prev_key, bool can_share, StripTaps<TX>& t) {
         float px, py;
         chunk_pos<GUARD>(hh, fx, (float)min(sy0 + k, g.H - 1), g, px, py);
         if constexpr (WIDE)
-            issue_taps_strip_wide(view + (int64_t)c * CH * 4, g, cg, j, c * CH + j < g.P, px, py, kstride, prev_key,
+            issue_taps_strip_wide<TX>(view + (int64_t)c * CH * 4, g, cg, j, c * CH + j < g.P, px, py, kstride, prev_key,
                                   can_share, t);
         else
             issue_taps_strip(make_rsrc(view + (int64_t)c * CH * 4, cg.rec_bytes), g, cg, j, c * CH + j < g.P, px, py,
                              kstride, prev_key, can_share, t);
     };
-    StripTaps T[NT];
-    f32x4 sc = {0.f, 0.f, 0.f, 0.f}, sd = sc;  // the previous row's south taps
+    StripTaps<TX> T[NT];
+    typename TX::Tap sc = TX::zero(), sd = sc;  // the previous row's south taps
     float hc[9];
     load_h(0, hc);
 #pragma unroll
@@ -492,7 +547,7 @@ __device__ __forceinline__ void render_chunk_wave_strip(const float* __restrict_
             }
         }
         if constexpr (SR % NT != 0) {  // the next chunk's rows sit at ring positions SR % NT ..: rotate
-            StripTaps tmp[NT];
+            StripTaps<TX> tmp[NT];
 #pragma unroll
             for (int q = 0; q < NT; ++q) tmp[q] = T[(q + SR) % NT];
 #pragma unroll
@@ -507,8 +562,9 @@ constexpr int kStripTX = 32;  // block tile width of the strip kernels (4 strips
 // One block = 4 waves = a 32 x SR output tile of one view (wave w: the 8 x SR strip at column
 // 8w); XCD-aware (tile, view) order, tile-level division proof.  Dynamic LDS as
 // render_chunk_kernel<8, 1, 1>.  WIDE: a view of 2 GiB or more (64-bit tap addresses, global loads).
-template <int SR, int NT, bool WIDE = false>
-__global__ __launch_bounds__(256, 3) void render_chunk_strip_kernel(const float* __restrict__ mpi, int64_t view_stride,
+// TX: the texel type; view_stride in its Scalars.
+template <int SR, int NT, bool WIDE = false, class TX = InF32>
+__global__ __launch_bounds__(256, 3) void render_chunk_strip_kernel(const typename TX::Scalar* __restrict__ mpi, int64_t view_stride,
                                                                     RenderGeom g, ChunkGeom cg, int V,
                                                                     const float* __restrict__ homs,
                                                                     float* __restrict__ out,
@@ -541,7 +597,7 @@ __global__ __launch_bounds__(256, 3) void render_chunk_strip_kernel(const float*
     const bool dead = __syncthreads_and(dd);
     const int sx0 = tx0 + wave * 8;
     if (sx0 >= g.W) return;  // whole wave; no barrier follows
-    const float* view = mpi + (int64_t)v * view_stride;
+    const typename TX::Scalar* view = mpi + (int64_t)v * view_stride;
     f32x4* slot = slots + wave * kWave * 9;
     const int x = sx0 + (lane & 7), y = ty0 + (lane >> 3);  // the pixel of half 0 (half h: row y + 8h)
     const int64_t HW = (int64_t)g.H * g.W;
@@ -564,10 +620,10 @@ __global__ __launch_bounds__(256, 3) void render_chunk_strip_kernel(const float*
             cr[hh] = r0; cgr[hh] = g0; cb[hh] = b0;
         }
     } else if (proven)
-        render_chunk_wave_strip<false, SR, NT, WIDE>(view, g, cg, hs, slot, sx0, ty0, lane, cr, cgr, cb, ck, HW,
+        render_chunk_wave_strip<false, SR, NT, WIDE, TX>(view, g, cg, hs, slot, sx0, ty0, lane, cr, cgr, cb, ck, HW,
                                                8 * (int64_t)g.W, nhk);
     else
-        render_chunk_wave_strip<true, SR, NT, WIDE>(view, g, cg, hs, slot, sx0, ty0, lane, cr, cgr, cb, ck, HW,
+        render_chunk_wave_strip<true, SR, NT, WIDE, TX>(view, g, cg, hs, slot, sx0, ty0, lane, cr, cgr, cb, ck, HW,
                                               8 * (int64_t)g.W, nhk);
 #pragma unroll
     for (int hh = 0; hh < SR / 8; ++hh) {

@@ -214,12 +214,27 @@ def mpi_render_view_f16(rgba_layers_f16, tgt_pose, planes, intrinsics):
     _lib.F16_FLOAT_ONCE_MIN_VIEWS views, where copy + float kernel beat the f16 kernel; below, and
     for a non-broadcast batch, the f16 kernel renders (a caller that renders one MPI many times
     packs it once and calls _lib.render_packed_f16, which routes a reused MPI from fewer views).
-    Inference only (no autograd through half texels).  An extension of the drop-in API."""
+    Training: when rgba_layers_f16 requires grad (grad enabled) the frame is differentiable w.r.t. it --
+    _lib.RenderF16Function: the half tensor is read in place at 8 B per texel by the training forward and
+    the adjoint (render_chunk.hip InF16), and rgba_layers_f16.grad arrives in float16, bit for bit
+    RN_half of the gradient mpi_render_view_torch(rgba_layers_f16.float(), ...) gives (which is what the
+    reference's autograd leaves in a half leaf), with no fp32 gradient and no float copy (but of the one
+    row or column of a degenerate frame, H or W < 2, for its forward frame).  A stride-0
+    batch gets one half gradient per view and autograd's expand backward sums them in half.  When
+    tgt_pose, planes or intrinsics requires grad the frame is differentiable w.r.t. them as in
+    mpi_render_view_torch, with the same bits.  With nothing requiring grad, or under no_grad, the
+    inference route above runs unchanged.  An extension of the drop-in API."""
     if not isinstance(rgba_layers_f16, torch.Tensor) or rgba_layers_f16.dtype != torch.float16:
         raise RuntimeError("mpi_render_view_f16 expects a float16 [B, H, W, P, 4] tensor")
     batch_size = tgt_pose.shape[0]
     n_planes = len(planes)
     depths = planes.reshape([n_planes, 1])
+    if rgba_layers_f16.is_cuda and _camera_grad(tgt_pose, planes, intrinsics):
+        if rgba_layers_f16.shape[0] != batch_size or rgba_layers_f16.shape[3] != n_planes:
+            raise RuntimeError(f"shape mismatch: MPI batch/planes {rgba_layers_f16.shape[0]}/{rgba_layers_f16.shape[3]} "
+                               f"vs poses/planes {batch_size}/{n_planes}")
+        homs = _host.render_homographies_autograd(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
+        return _lib.RenderF16Function.apply(rgba_layers_f16, homs.to(rgba_layers_f16.device))
     if tgt_pose.is_cuda:
         homs = _host.render_homographies_device(tgt_pose, depths.reshape(-1), intrinsics, batch_size)
     else:
@@ -228,15 +243,9 @@ def mpi_render_view_f16(rgba_layers_f16, tgt_pose, planes, intrinsics):
     if B != batch_size or P != n_planes:
         raise RuntimeError(f"shape mismatch: MPI batch/planes {B}/{P} vs poses/planes {batch_size}/{n_planes}")
     homs = homs.reshape(B, P, 9)
-    if B > 1 and rgba_layers_f16.stride(0) == 0:  # one MPI, many views: pack once
-        return _lib.render_packed_f16(_lib.pack_planes_f16(rgba_layers_f16[0]), homs,
-                                      route_float=B >= _lib.F16_FLOAT_ONCE_MIN_VIEWS)
-    out = torch.empty((B, H, W, 3), device=rgba_layers_f16.device, dtype=torch.float32)
-    packed = None
-    for b in range(B):
-        packed = _lib.pack_planes_f16(rgba_layers_f16[b], out=packed)
-        _lib.render_packed_f16(packed, homs[b:b + 1], out=out[b:b + 1], route_float=False)
-    return out
+    if torch.is_grad_enabled() and rgba_layers_f16.requires_grad:
+        return _lib.RenderF16Function.apply(rgba_layers_f16, homs)
+    return _lib.render_f16_views(rgba_layers_f16, homs)  # (pack + packed render, view by view or once)
 
 
 def _plane_color_mpi(rgba_layers, plane_colors):

@@ -37,11 +37,23 @@ def mpi_from_net_output(mpi_pred, ref_img, num_mpi_planes):
     return fn(mpi_pred, {"mpi_planes": torch.zeros((B, num_mpi_planes)), "ref_img": ref_img})
 
 
+def ga_inputs(ref):
+    """The `ga` case's generator (as the case's dout then draws from it), intrinsics, poses and depths
+    (tools/gen_goldens_f16grad.py renders the same cameras over a half MPI)."""
+    g = torch.Generator().manual_seed(77)
+    Ka = f32([configs.intrinsics_matrix(60.0, 63.0, 28.0, 19.5), configs.intrinsics_matrix(58.0, 58.0, 30.0, 21.0)])
+    pa = f32([configs.pose_from(configs.rot_y(2.0), (0.06, -0.03, 0.05)), rand_pose(g, 0.04, 0.08)])
+    return g, Ka, pa, f32(ref.inv_depths(1, 100, 6))
+
+
+GA_SHAPE = (2, 40, 56, 6, 31)  # B, H, W, P, MPI seed of `ga`
+
+
 def main():
     torch.set_num_threads(8)
     ref = load_reference()
     out = {}
-    g = torch.Generator().manual_seed(77)
+    g, Ka, pa, da = ga_inputs(ref)
 
     def case(name, B, H, W, P, seed, K, poses, depths, broadcast=False, alpha_fn=None):
         mpi = configs.synthetic_mpi(1 if broadcast else B, H, W, P, seed)
@@ -57,9 +69,7 @@ def main():
                     f"{name}_out": res.detach().numpy(), f"{name}_dout": dout.numpy(),
                     f"{name}_grad": leaf.grad.numpy()})
 
-    Ka = f32([configs.intrinsics_matrix(60.0, 63.0, 28.0, 19.5), configs.intrinsics_matrix(58.0, 58.0, 30.0, 21.0)])
-    pa = f32([configs.pose_from(configs.rot_y(2.0), (0.06, -0.03, 0.05)), rand_pose(g, 0.04, 0.08)])
-    case("ga", 2, 40, 56, 6, 31, Ka, pa, f32(ref.inv_depths(1, 100, 6)))
+    case("ga", *GA_SHAPE, Ka, pa, da)
     Kb = f32([configs.intrinsics_matrix(40.0, 42.0, 24.0, 18.0)])
     case("gbig", 1, 36, 48, 5, 32, Kb, f32([rand_pose(g, 0.8, 1.5)]), f32(ref.inv_depths(0.5, 10, 5)))
 
