@@ -395,6 +395,22 @@ int mpiv_inverse_warp(const float *img, const int64_t img_strides[4], int B, int
                       const float *ki, const float *proj, const float *depth, const int64_t depth_strides[3],
                       int Ht, int Wt, float *out, void *stream);
 
+/* The adjoint of mpiv_inverse_warp (warp_bwd.hip): gradients of sum(out * dout) w.r.t. the depth map,
+ * the source image and the two camera matrices, for the forward's arguments.
+ * dout:   [B,Ht,Wt,C] element strides dout_strides[4] (any, a stride-0 broadcast included)
+ * ddepth: [B,Ht,Wt] contiguous, dimg: [B,Hs,Ws,C] contiguous, dki: [B][9], dproj: [B][16] (row 3
+ *         written as +0); NULL for a gradient that is not wanted (at least one is).
+ * ddepth and dimg are the reference's CPU autograd bits; dki and dproj are frame sums in a fixed order
+ * of their own, the same bits whatever else is requested.  workspace: 16-byte aligned, at least
+ * mpiv_inverse_warp_backward_workspace_size bytes (0: a size the kernels cannot index, Ht*Wt or
+ * (Hs+1)*(Ws+1) >= 2^31, which the entry refuses).  No allocation and no synchronisation inside. */
+size_t mpiv_inverse_warp_backward_workspace_size(int B, int Hs, int Ws, int C, int Ht, int Wt);
+int mpiv_inverse_warp_backward(const float *img, const int64_t img_strides[4], int B, int Hs, int Ws, int C,
+                               const float *ki, const float *proj, const float *depth,
+                               const int64_t depth_strides[3], int Ht, int Wt, const float *dout,
+                               const int64_t dout_strides[4], float *ddepth, float *dimg, float *dki, float *dproj,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- sampling / compositing primitives ---------------------------------- */
 
 /* bilinear_wrapper_torch (utils.py:104-134) / resampler_wrapper_torch

@@ -326,6 +326,48 @@ def psv_matrices(src_intrinsics: torch.Tensor, tgt_intrinsics: torch.Tensor, pos
     return ki, proj
 
 
+def _host_like(x: torch.Tensor) -> torch.Tensor:
+    """cpu32_like on the autograd graph: an fp32 CPU tensor with x's values, size and strides whose
+    gradient returns to x (a device tensor's storage span comes over in one differentiable copy and is
+    re-viewed with x's strides, so torch.inverse sees the caller's layout)."""
+    if x.device.type == "cpu" and x.dtype == _F32:
+        return x
+    if x.is_contiguous() or x.numel() == 0:
+        return x.to(device=_CPU, dtype=_F32)
+    span = 1 + sum((n - 1) * st for n, st in zip(x.shape, x.stride()))
+    flat = torch.as_strided(x, (span,), (1,), x.storage_offset()).to(device=_CPU, dtype=_F32)
+    return torch.as_strided(flat, x.shape, x.stride())
+
+
+def psv_matrices_autograd(src_intrinsics: torch.Tensor, tgt_intrinsics: torch.Tensor, pose: torch.Tensor):
+    """psv_matrices WITHOUT the detach: the reference's ops on CPU in fp32 -- torch.inverse on the caller's
+    K_tgt as laid out (utils.py:370), the two cats and the matmul (utils.py:431-438) -- as nodes of the
+    autograd graph of the intrinsics and the pose, so d warp / d (Ki, proj) (warp_bwd.hip) flows on to
+    them through the very torch ops the reference differentiates.  Values equal psv_matrices bit for bit.
+    Returns (ki [B,9], proj [B,16]) fp32 CPU tensors; the caller moves them to the device with .to(), whose
+    autograd node carries the gradients back.
+
+    A device tensor comes to the host through a differentiable copy, one blocking device-to-host copy per
+    call and device tensor; the no-gradient routes (psv_matrices_device) have none.  Under a HIP-graph
+    capture that copy cannot be recorded: raises (_lib.host_under_capture) before anything is launched."""
+    from . import _lib
+    if torch.cuda.is_available():
+        _lib.host_under_capture("the inverse warp's camera chain (pose, intrinsics)")
+    pose = pose.to(device=_CPU, dtype=_F32)
+    B = pose.shape[0]
+    kt = _host_like(tgt_intrinsics)
+    if kt.dim() == 2:
+        kt = kt.unsqueeze(0)
+    ki = torch.inverse(kt).contiguous()  # the caller's layout (psv_inverse)
+    if ki.shape[0] != B:
+        ki = ki.expand(B, 3, 3).contiguous()
+    Ks = src_intrinsics.to(device=_CPU, dtype=_F32).expand(B, 3, 3)
+    k4 = torch.cat([Ks, torch.zeros(B, 3, 1)], dim=2)
+    k4 = torch.cat([k4, torch.tensor([[[0.0, 0.0, 0.0, 1.0]]]).repeat(B, 1, 1)], dim=1)
+    proj = torch.matmul(k4, pose)
+    return ki.reshape(B, 9).contiguous(), proj.reshape(B, 16).contiguous()
+
+
 def psv_ki_device(tgt_intrinsics: torch.Tensor, batch: int, dev, sid=None) -> torch.Tensor:
     """Ki = inverse(K_tgt) [batch, 3, 3] (contiguous: read as [batch, 9]) on dev, memoised per
     intrinsics tensor (_kinv_device), inverted in the caller's layout (psv_inverse)."""

@@ -114,7 +114,14 @@ _SIGS_F16_TRAIN = {
     "mpiv_render_backward_watched_f16": _SIGS["mpiv_render_backward_watched"],
     "mpiv_render_backward_cam_f16": _SIGS_CAM["mpiv_render_backward_cam"],
 }
-EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_F16_TRAIN) + ("mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
+# the inverse warp's adjoint (warp_bwd.hip): on its own for the same reason; its side-stream and graph-replay
+# cases are in tests/test_warpgrad_gpu.py.
+_SIGS_WARP = {
+    "mpiv_inverse_warp_backward": [_vp, _c_i64p, _int, _int, _int, _int, _vp, _vp, _vp, _c_i64p, _int, _int, _vp,
+                                   _c_i64p, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+}
+EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_F16_TRAIN) + tuple(_SIGS_WARP) + (
+                          "mpiv_inverse_warp_backward_workspace_size","mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
                           "mpiv_render_backward_abort_flag",
                           "mpiv_render_backward_workspace_size_min", "mpiv_render_backward_cam_workspace_size",
                           "mpiv_render_backward_cam_workspace_size_min", "mpiv_build_id", "mpiv_debug_set")
@@ -176,7 +183,8 @@ def _open(path: str, check_id: bool):
                            "(python -c 'import __graft_entry__ as g; g.build()')")
     L.mpiv_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int]
     L.mpiv_debug_set.restype = ctypes.c_int
-    for name, args in (*_SIGS.items(), *_SIGS_CAM.items(), *_SIGS_ALPHA.items(), *_SIGS_F16_TRAIN.items()):
+    for name, args in (*_SIGS.items(), *_SIGS_CAM.items(), *_SIGS_ALPHA.items(), *_SIGS_F16_TRAIN.items(),
+                       *_SIGS_WARP.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int
@@ -189,6 +197,8 @@ def _open(path: str, check_id: bool):
     for fn in (L.mpiv_render_backward_cam_workspace_size, L.mpiv_render_backward_cam_workspace_size_min):
         fn.argtypes = [_int, _int, _int]
         fn.restype = ctypes.c_size_t
+    L.mpiv_inverse_warp_backward_workspace_size.argtypes = [_int] * 6
+    L.mpiv_inverse_warp_backward_workspace_size.restype = ctypes.c_size_t
     L.mpiv_render_backward_abort_flag.argtypes = [_int]
     L.mpiv_render_backward_abort_flag.restype = ctypes.c_void_p
     if L.mpiv_abi_version() != ABI_VERSION:
@@ -1478,6 +1488,57 @@ def inverse_warp_depthmap(img, depth, ki, proj, tgt_h, tgt_w):
     _call("mpiv_inverse_warp", img, _strides(img), B, Hs, Ws, C, _up(ki, dev, "ki"), _up(proj, dev, "proj"),
           depth, _strides(depth), tgt_h, tgt_w, out, _stream(dev))
     return out
+
+
+def inverse_warp_backward(img, depth, ki, proj, dout, want=(True, True, True, True), workspace=None):
+    """The adjoint of inverse_warp_depthmap (mpiv_inverse_warp_backward, warp_bwd.hip): for dout
+    [B,Ht,Wt,C] (read by its element strides: a stride-0 or permuted gradient is not copied) returns
+    (dimg [B,Hs,Ws,C], ddepth [B,Ht,Wt], dki [B,9], dproj [B,16]) on the device, None where `want` says
+    so.  dimg and ddepth are the reference's CPU autograd bits; dki and dproj are reproducible frame sums.
+    One call on the current stream; the workspace (mpiv_inverse_warp_backward_workspace_size bytes) is
+    the caller's or a torch.empty on the same stream."""
+    dev = _dev(img, depth, dout)
+    B, Hs, Ws, C = img.shape
+    _, Ht, Wt = depth.shape
+    if tuple(dout.shape) != (B, Ht, Wt, C):
+        raise RuntimeError(f"grad_output must be [{B},{Ht},{Wt},{C}], got {tuple(dout.shape)}")
+    if not any(want):
+        raise RuntimeError("inverse_warp_backward: nothing to compute")
+    need = load().mpiv_inverse_warp_backward_workspace_size(B, Hs, Ws, C, Ht, Wt)
+    ws = workspace if workspace is not None else torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
+        raise RuntimeError(f"workspace must be a contiguous uint8 tensor on {dev}")
+    new = lambda on, *shape: torch.empty(shape, device=dev, dtype=torch.float32) if on else None  # noqa: E731
+    dimg, ddepth, dki, dproj = new(want[0], B, Hs, Ws, C), new(want[1], B, Ht, Wt), new(want[2], B, 9), new(want[3], B, 16)
+    _call("mpiv_inverse_warp_backward", img, _strides(img), B, Hs, Ws, C, _up(ki, dev, "ki"), _up(proj, dev, "proj"),
+          depth, _strides(depth), Ht, Wt, dout, _strides(dout), ddepth, dimg, dki, dproj, ws, ws.numel(), _stream(dev))
+    return dimg, ddepth, dki, dproj
+
+
+class InverseWarpFunction(torch.autograd.Function):
+    """Autograd node of the depth-map inverse warp: forward = inverse_warp_depthmap() (the same launch and
+    the same bits as the no-grad call), backward = inverse_warp_backward() w.r.t. whichever of img, depth,
+    ki [B,9] and proj [B,16] require grad (ki and proj then are device tensors at the end of
+    _host.psv_matrices_autograd's chain from pose and intrinsics)."""
+
+    @staticmethod
+    def forward(ctx, img, depth, ki, proj, tgt_h, tgt_w):
+        dev = _dev(img, depth)
+        ki_d, proj_d = _up(ki.detach(), dev, "ki"), _up(proj.detach(), dev, "proj")
+        ctx.save_for_backward(img, depth, ki_d, proj_d)
+        ctx.mat_shapes = (tuple(ki.shape), tuple(proj.shape))
+        return inverse_warp_depthmap(img, depth, ki_d, proj_d, tgt_h, tgt_w)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        img, depth, ki, proj = ctx.saved_tensors
+        dimg, ddepth, dki, dproj = inverse_warp_backward(img, depth, ki, proj, dout, ctx.needs_input_grad[:4])
+        if dki is not None:
+            dki = dki.reshape(ctx.mat_shapes[0])
+        if dproj is not None:
+            dproj = dproj.reshape(ctx.mat_shapes[1])
+        return dimg, ddepth, dki, dproj, None, None
 
 
 # ---------------------------------------------------------------------------

@@ -25,6 +25,7 @@
 #include "render_bwd.hip"
 #include "render_bwd_cam.hip"
 #include "sweep.hip"
+#include "warp_bwd.hip"
 #include "geometry.hip"
 #include "assemble.hip"
 #include "synth.hip"
@@ -1901,6 +1902,93 @@ int mpiv_inverse_warp(const float* img, const int64_t st[4], int B, int Hs, int 
     inverse_warp_kernel<<<grid, 256, 0, S(stream)>>>(img, s, sweep_params(B, Hs, Ws, C, 1, Ht, Wt), ki, proj, depth,
                                                      dst[0], dst[1], dst[2], out);
     return launched("mpiv_inverse_warp");
+}
+
+// The workspace of mpiv_inverse_warp_backward: per view the sample positions, two key and two id arrays
+// of the sort, the digit histograms and totals and the camera partials, each part 256-byte aligned.
+static size_t warp_bwd_layout(int B, int64_t n, WarpBwdWs* ws, char* base) {
+    const size_t nblk = (size_t)((n + kWarpThreads - 1) / kWarpThreads);
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base ? base + off : nullptr;
+        off += (bytes + 255) & ~(size_t)255;
+        return p;
+    };
+    char* pos = take((size_t)B * n * sizeof(float2));
+    char* k0 = take((size_t)B * n * 4);
+    char* k1 = take((size_t)B * n * 4);
+    char* i0 = take((size_t)B * n * 4);
+    char* i1 = take((size_t)B * n * 4);
+    char* hist = take((size_t)B * 256 * nblk * 4);
+    char* tot = take((size_t)B * 256 * 4);
+    char* part = take((size_t)B * nblk * kWarpCam * 4);
+    if (ws) {
+        ws->pos = reinterpret_cast<float2*>(pos);
+        ws->key[0] = reinterpret_cast<unsigned*>(k0);
+        ws->key[1] = reinterpret_cast<unsigned*>(k1);
+        ws->id[0] = reinterpret_cast<unsigned*>(i0);
+        ws->id[1] = reinterpret_cast<unsigned*>(i1);
+        ws->hist = reinterpret_cast<unsigned*>(hist);
+        ws->totals = reinterpret_cast<unsigned*>(tot);
+        ws->partials = reinterpret_cast<float*>(part);
+    }
+    return off;
+}
+
+// sizes the kernels cannot index: pixel and texel ids and the sort's keys (bucket ids up to
+// (Hs+1)*(Ws+1), the "no bucket" key) are 31-bit
+static bool warp_bwd_too_large(int Hs, int Ws, int Ht, int Wt) {
+    return (int64_t)Ht * Wt >= ((int64_t)1 << 31) || (int64_t)(Hs + 1) * (Ws + 1) >= ((int64_t)1 << 31);
+}
+
+size_t mpiv_inverse_warp_backward_workspace_size(int B, int Hs, int Ws, int C, int Ht, int Wt) {
+    if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0 || warp_bwd_too_large(Hs, Ws, Ht, Wt)) return 0;
+    return warp_bwd_layout(B, (int64_t)Ht * Wt, nullptr, nullptr);
+}
+
+int mpiv_inverse_warp_backward(const float* img, const int64_t st[4], int B, int Hs, int Ws, int C, const float* ki,
+                               const float* proj, const float* depth, const int64_t dst[3], int Ht, int Wt,
+                               const float* dout, const int64_t dost[4], float* ddepth, float* dimg, float* dki,
+                               float* dproj, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* nm = "mpiv_inverse_warp_backward";
+    if (!img || !st || !ki || !proj || !depth || !dst || !dout || !dost || !workspace)
+        return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (!ddepth && !dimg && !dki && !dproj) return fail(MPIV_ERR_ARG, "%s: no gradient requested", nm);
+    if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if (B > kMaxGridYZ) return fail(MPIV_ERR_ARG, "%s: too large", nm);
+    if (warp_bwd_too_large(Hs, Ws, Ht, Wt))
+        return fail(MPIV_ERR_ARG, "%s: one view is limited to Ht*Wt < 2^31 pixels and (Hs+1)*(Ws+1) < 2^31 buckets "
+                    "(the sort's key width)", nm);
+    const int64_t n = (int64_t)Ht * Wt, ntex = (int64_t)Hs * Ws;
+    WarpBwdWs ws;
+    const size_t need = warp_bwd_layout(B, n, &ws, static_cast<char*>(workspace));
+    if (!aligned16(workspace) || workspace_bytes < need)
+        return fail(MPIV_ERR_ARG, "%s: workspace must be 16-byte aligned and hold %zu bytes "
+                    "(mpiv_inverse_warp_backward_workspace_size)", nm, need);
+    hipStream_t q = S(stream);
+    const SweepParams sp = sweep_params(B, Hs, Ws, C, 1, Ht, Wt);
+    const ImgStrides s{st[0], st[1], st[2], st[3]}, ds{dost[0], dost[1], dost[2], dost[3]};
+    const unsigned nblk = blocks(n, kWarpThreads);
+    const bool cam = dki || dproj;
+    warp_bwd_pixel_kernel<<<dim3(nblk, B, 1), kWarpThreads, 0, q>>>(
+        img, s, sp, ki, proj, depth, dst[0], dst[1], dst[2], dout, ds, ddepth, dimg ? ws.pos : nullptr,
+        dimg ? ws.key[0] : nullptr, cam ? ws.partials : nullptr, nblk);
+    if (cam) warp_bwd_cam_sum_kernel<<<B, 256, 0, q>>>(ws.partials, nblk, dki, dproj);
+    if (dimg) {
+        int bits = 0;  // of the largest key, the "no bucket" id (Hs+1)*(Ws+1)
+        while (((int64_t)(Hs + 1) * (Ws + 1)) >> bits) ++bits;
+        const int passes = (bits + 7) / 8;
+        int cur = 0;
+        for (int p = 0; p < passes; ++p, cur ^= 1) {
+            warp_sort_hist_kernel<<<dim3(nblk, B, 1), kWarpThreads, 0, q>>>(ws.key[cur], (unsigned)n, nblk, 8 * p, ws.hist);
+            warp_sort_scan_kernel<<<dim3(256, B, 1), 256, 0, q>>>(ws.hist, nblk, ws.totals);
+            warp_sort_scatter_kernel<<<dim3(nblk, B, 1), kWarpThreads, 0, q>>>(
+                ws.key[cur], p == 0 ? nullptr : ws.id[cur], ws.key[cur ^ 1], ws.id[cur ^ 1], ws.hist, ws.totals, (unsigned)n, nblk, 8 * p);
+        }
+        warp_bwd_gather_kernel<<<dim3(blocks(ntex, 256), B, 1), 256, 0, q>>>(ws.key[cur], ws.id[cur], ws.pos, dout, ds, sp,
+                                                                            make_fastdiv((unsigned)Wt), dimg);
+    }
+    return launched(nm);
 }
 
 int mpiv_grid_sample(const float* in, const int64_t ist[4], int N, int C, int Hi, int Wi, const float* coords,

@@ -378,6 +378,8 @@ def projective_inverse_warp_torch(img, depth, pose, intrinsics, ret_flows=False)
         raise RuntimeError("projective_inverse_warp_torch: ret_flows=True is not supported "
                            "(the reference raises a shape mismatch, utils.py:447-448)")
     batch, height, width, _ = img.shape
+    if _warp_grad(img, depth, pose, intrinsics):
+        return _warp_autograd(img, depth, pose, intrinsics, intrinsics, height, width)
     ki, proj = _warp_matrices(img, pose, intrinsics, intrinsics)
     return _lib.inverse_warp_depthmap(img, depth, ki, proj, height, width)
 
@@ -415,6 +417,25 @@ def _warp_matrices(img, pose, src_intrinsics, tgt_intrinsics):
     return _host.psv_matrices(src_intrinsics, tgt_intrinsics, pose)
 
 
+def _warp_grad(img, depth, *cameras):
+    """The inverse warp's differentiable route: grad enabled, a device image, and any input requiring grad."""
+    return (torch.is_grad_enabled() and img.is_cuda
+            and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (img, depth, *cameras)))
+
+
+def _warp_autograd(img, depth, pose, src_intrinsics, tgt_intrinsics, tgt_height, tgt_width):
+    """projective_inverse_warp_torch[2] as a node of the autograd graph (_lib.InverseWarpFunction): the same
+    forward launch and bits, gradients for img, depth, pose and the intrinsics, those of img and depth
+    bit-exact to the reference's CPU autograd.  The matrices come from the no-grad routes unless a camera
+    input requires grad; then from _host.psv_matrices_autograd's chain on the host (not capturable)."""
+    if any(t.requires_grad for t in (pose, src_intrinsics, tgt_intrinsics)):
+        ki, proj = _host.psv_matrices_autograd(src_intrinsics, tgt_intrinsics, pose)
+        ki, proj = ki.to(img.device), proj.to(img.device)
+    else:
+        ki, proj = _warp_matrices(img, pose, src_intrinsics, tgt_intrinsics)
+    return _lib.InverseWarpFunction.apply(img, depth, ki, proj, tgt_height, tgt_width)
+
+
 def format_network_input_torch(self, ref_image, psv_src_images, ref_pose, psv_src_poses, planes, intrinsics):
     """Network input [B, H, W, 3 + S*D*3]: the reference image followed by one plane-sweep
     volume per extra source (utils.py:473-498; the unused leading `self` is kept).
@@ -439,6 +460,8 @@ def projective_inverse_warp_torch2(img, depth, pose, src_intrinsics, tgt_intrins
     if ret_flows:
         raise RuntimeError("projective_inverse_warp_torch2: ret_flows=True is not supported "
                            "(the reference raises a shape mismatch, utils.py:766-767)")
+    if _warp_grad(img, depth, pose, src_intrinsics, tgt_intrinsics):
+        return _warp_autograd(img, depth, pose, src_intrinsics, tgt_intrinsics, tgt_height, tgt_width)
     ki, proj = _warp_matrices(img, pose, src_intrinsics, tgt_intrinsics)
     return _lib.inverse_warp_depthmap(img, depth, ki, proj, tgt_height, tgt_width)
 
