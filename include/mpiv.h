@@ -411,6 +411,33 @@ int mpiv_inverse_warp_backward(const float *img, const int64_t img_strides[4], i
                                const int64_t dout_strides[4], float *ddepth, float *dimg, float *dki, float *dproj,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/* The adjoint of mpiv_plane_sweep (psv_bwd.hip): gradients of sum(volume * dout) w.r.t. the source image,
+ * the D plane depths and the two camera matrices, for the forward's arguments.  The reference's sweep is D
+ * inverse warps on constant depth maps and a cat on the channel axis, so this is D of
+ * mpiv_inverse_warp_backward's adjoints over one source in one call.
+ * dout:    [B,Ht,Wt,D*C] element strides dout_strides[4] (any; depth d owns channels d*C .. d*C+C-1)
+ * dimg:    [B,Hs,Ws,C] contiguous: ((g_{D-1} + g_{D-2}) + ...) + g_0 with g_d the inverse warp's dimg for
+ *          depth d, the order (and the bits) of the reference's CPU autograd
+ * ddepths: [D], entry d the sum over B*Ht*Wt of the inverse warp's per-pixel ddepth at depth d
+ * dki:     [B][9], dproj: [B][16] (row 3 written as +0): the sums over the depths of the inverse warp's
+ *          frame sums
+ * NULL for a gradient that is not wanted (at least one is).  The sums are accumulated in double in a fixed
+ * order and rounded once: the same bits whatever else is requested and however the planes are grouped.
+ * workspace: 16-byte aligned.  mpiv_plane_sweep_backward_workspace_size bytes take all planes in one
+ * group; any size from mpiv_plane_sweep_backward_workspace_size_min (one plane per group) up is accepted
+ * and the entry picks the largest group that fits (the results' bits do not depend on it).  Per group of
+ * G planes: B*G*(24*Ht*Wt + 1024*(ceil(Ht*Wt/256) + 1) + 8*(Hs+1)*(Ws+1)) bytes, plus
+ * 88*B*D*ceil(Ht*Wt/256) bytes of partial sums, each array rounded up to 256 bytes.  Both size functions
+ * return 0 for a size the kernels cannot index (Ht*Wt, (Hs+1)*(Ws+1), D*C or B*D*ceil(Ht*Wt/256) >= 2^31,
+ * B > 65535), which the entry refuses before launching anything.  No allocation and no synchronisation
+ * inside; every argument check runs before the first HIP call. */
+size_t mpiv_plane_sweep_backward_workspace_size(int B, int Hs, int Ws, int C, int Ht, int Wt, int D);
+size_t mpiv_plane_sweep_backward_workspace_size_min(int B, int Hs, int Ws, int C, int Ht, int Wt, int D);
+int mpiv_plane_sweep_backward(const float *img, const int64_t img_strides[4], int B, int Hs, int Ws, int C,
+                              const float *ki, const float *proj, const float *depths, int D, int Ht, int Wt,
+                              const float *dout, const int64_t dout_strides[4], float *dimg, float *ddepths,
+                              float *dki, float *dproj, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- sampling / compositing primitives ---------------------------------- */
 
 /* bilinear_wrapper_torch (utils.py:104-134) / resampler_wrapper_torch

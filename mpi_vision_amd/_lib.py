@@ -120,7 +120,14 @@ _SIGS_WARP = {
     "mpiv_inverse_warp_backward": [_vp, _c_i64p, _int, _int, _int, _int, _vp, _vp, _vp, _c_i64p, _int, _int, _vp,
                                    _c_i64p, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
 }
-EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_F16_TRAIN) + tuple(_SIGS_WARP) + (
+# the plane sweep's adjoint (psv_bwd.hip): on its own for the same reason; its side-stream and graph-replay
+# cases are in tests/test_psvgrad_gpu.py.
+_SIGS_PSV = {
+    "mpiv_plane_sweep_backward": [_vp, _c_i64p, _int, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp,
+                                  _c_i64p, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
+}
+EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_F16_TRAIN) + tuple(_SIGS_WARP) + tuple(_SIGS_PSV) + (
+                          "mpiv_plane_sweep_backward_workspace_size", "mpiv_plane_sweep_backward_workspace_size_min",
                           "mpiv_inverse_warp_backward_workspace_size","mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
                           "mpiv_render_backward_abort_flag",
                           "mpiv_render_backward_workspace_size_min", "mpiv_render_backward_cam_workspace_size",
@@ -184,7 +191,7 @@ def _open(path: str, check_id: bool):
     L.mpiv_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int]
     L.mpiv_debug_set.restype = ctypes.c_int
     for name, args in (*_SIGS.items(), *_SIGS_CAM.items(), *_SIGS_ALPHA.items(), *_SIGS_F16_TRAIN.items(),
-                       *_SIGS_WARP.items()):
+                       *_SIGS_WARP.items(), *_SIGS_PSV.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int
@@ -199,6 +206,9 @@ def _open(path: str, check_id: bool):
         fn.restype = ctypes.c_size_t
     L.mpiv_inverse_warp_backward_workspace_size.argtypes = [_int] * 6
     L.mpiv_inverse_warp_backward_workspace_size.restype = ctypes.c_size_t
+    for fn in (L.mpiv_plane_sweep_backward_workspace_size, L.mpiv_plane_sweep_backward_workspace_size_min):
+        fn.argtypes = [_int] * 7
+        fn.restype = ctypes.c_size_t
     L.mpiv_render_backward_abort_flag.argtypes = [_int]
     L.mpiv_render_backward_abort_flag.restype = ctypes.c_void_p
     if L.mpiv_abi_version() != ABI_VERSION:
@@ -1539,6 +1549,135 @@ class InverseWarpFunction(torch.autograd.Function):
         if dproj is not None:
             dproj = dproj.reshape(ctx.mat_shapes[1])
         return dimg, ddepth, dki, dproj, None, None
+
+
+def plane_sweep_backward(img, depths, ki, proj, dout, want=(True, True, True, True), workspace=None):
+    """The adjoint of plane_sweep (mpiv_plane_sweep_backward, psv_bwd.hip): img [B,Hs,Ws,C] (any strides),
+    depths a fp32 device tensor [D], dout [B,Ht,Wt,D*C] (read by its element strides: a channel slice of a
+    wider gradient is not copied).  Returns (dimg [B,Hs,Ws,C], ddepths [D], dki [B,9], dproj [B,16]) on the
+    device, None where `want` says so.  dimg is the reference's CPU autograd bits (the D per-depth
+    gradients added in descending d); ddepths, dki and dproj are reproducible sums.  One call on the
+    current stream; the workspace is the caller's (any size from
+    mpiv_plane_sweep_backward_workspace_size_min up: the planes are taken in groups that fit, with the same
+    bits) or a torch.empty of mpiv_plane_sweep_backward_workspace_size bytes on the same stream."""
+    dev = _dev(img, depths, dout)
+    B, Hs, Ws, C = img.shape
+    D = depths.numel()
+    if depths.dtype != torch.float32 or not depths.is_contiguous():
+        raise RuntimeError("plane_sweep_backward: depths must be a contiguous fp32 tensor")
+    if D == 0 or dout.dim() != 4 or dout.shape[0] != B or dout.shape[3] != D * C:
+        raise RuntimeError(f"grad_output must be [{B},Ht,Wt,{D * C}], got {tuple(dout.shape)}")
+    Ht, Wt = dout.shape[1], dout.shape[2]
+    if not any(want):
+        raise RuntimeError("plane_sweep_backward: nothing to compute")
+    if workspace is None:
+        need = load().mpiv_plane_sweep_backward_workspace_size(B, Hs, Ws, C, Ht, Wt, D)
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    else:
+        ws = workspace
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
+        raise RuntimeError(f"workspace must be a contiguous uint8 tensor on {dev}")
+    new = lambda on, *shape: torch.empty(shape, device=dev, dtype=torch.float32) if on else None  # noqa: E731
+    dimg, ddepths, dki, dproj = new(want[0], B, Hs, Ws, C), new(want[1], D), new(want[2], B, 9), new(want[3], B, 16)
+    _call("mpiv_plane_sweep_backward", img, _strides(img), B, Hs, Ws, C, _up(ki, dev, "ki"), _up(proj, dev, "proj"),
+          depths, D, Ht, Wt, dout, _strides(dout), dimg, ddepths, dki, dproj, ws, ws.numel(), _stream(dev))
+    return dimg, ddepths, dki, dproj
+
+
+class PlaneSweepFunction(torch.autograd.Function):
+    """Autograd node of the plane sweep: forward = plane_sweep()'s entry call (the same launch and the
+    same bits as the no-grad call), backward = plane_sweep_backward() w.r.t. whichever of img, depths [D],
+    ki [B,9] and proj [B,16] require grad (ki and proj then are device tensors at the end of
+    _host.psv_matrices_autograd's chain from pose and intrinsics).  img is [B,Hs,Ws,C] with any strides;
+    the depths enter as a tensor (a Python list has no gradient: the caller passes its device copy)."""
+
+    @staticmethod
+    def forward(ctx, img, depths, ki, proj, tgt_h, tgt_w):
+        dev = _dev(img)
+        dd = depths.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        ki_d, proj_d = _up(ki.detach(), dev, "ki"), _up(proj.detach(), dev, "proj")
+        ctx.save_for_backward(img, dd, ki_d, proj_d)
+        ctx.shapes = (tuple(depths.shape), tuple(ki.shape), tuple(proj.shape))
+        ctx.depths_on = (depths.device, depths.dtype)
+        B, Hs, Ws, C = img.shape
+        D = dd.shape[0]
+        out = torch.empty((B, tgt_h, tgt_w, D * C), device=dev, dtype=torch.float32)
+        _call("mpiv_plane_sweep", img, _strides(img), B, Hs, Ws, C, ki_d, proj_d, dd, D, tgt_h, tgt_w, out, _stream(dev))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        img, dd, ki, proj = ctx.saved_tensors
+        dimg, ddepths, dki, dproj = plane_sweep_backward(img, dd, ki, proj, dout, ctx.needs_input_grad[:4])
+        if ddepths is not None:
+            ddepths = ddepths.reshape(ctx.shapes[0]).to(device=ctx.depths_on[0], dtype=ctx.depths_on[1])
+        if dki is not None:
+            dki = dki.reshape(ctx.shapes[1])
+        if dproj is not None:
+            dproj = dproj.reshape(ctx.shapes[2])
+        return dimg, ddepths, dki, dproj, None, None
+
+
+class NetworkInputFunction(torch.autograd.Function):
+    """Autograd node of format_network_input_torch's tensor: forward = network_input()'s calls (the
+    reference image copied into the leading channels, each source's strided channel slice swept straight
+    into its channel range: the same launches and bits), backward = the leading slice of dout for
+    ref_image and, per source, plane_sweep_backward() of its slice of psv_src_images against its own
+    channel slice of dout, both read in place by their strides.  mats = (ki_0, proj_0, ki_1, proj_1, ...),
+    one pair per source ([B,9], [B,16]; device tensors at the end of the host chain when a camera requires
+    grad).  A depths tensor that requires grad gets the sum of the sources' ddepths."""
+
+    @staticmethod
+    def forward(ctx, ref_image, psv_src_images, depths, *mats):
+        dev = _dev(ref_image, psv_src_images)
+        S = len(mats) // 2
+        dd = depths.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        mats_d = [_up(m.detach(), dev, "ki" if i % 2 == 0 else "proj") for i, m in enumerate(mats)]
+        ctx.save_for_backward(psv_src_images, dd, *mats_d)
+        ctx.shapes = (tuple(depths.shape), [tuple(m.shape) for m in mats])
+        ctx.depths_on = (depths.device, depths.dtype)
+        B, H, W, _ = ref_image.shape
+        D = dd.shape[0]
+        Ctot = 3 + S * D * 3
+        out = torch.empty((B, H, W, Ctot), device=dev, dtype=torch.float32)
+        out[..., :3].copy_(ref_image)
+        for i in range(S):
+            src = psv_src_images[:, :, :, i * 3:(i + 1) * 3]
+            _call("mpiv_plane_sweep_into", src, _strides(src), B, H, W, 3, mats_d[2 * i], mats_d[2 * i + 1], dd, D, H, W,
+                  out[..., 3 + i * D * 3:], H * W * Ctot, Ctot, _stream(dev))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        psv_src_images, dd, *mats = ctx.saved_tensors
+        S, D = len(mats) // 2, dd.shape[0]
+        need = ctx.needs_input_grad
+        dref = dout[..., :3] if need[0] else None
+        want_d = need[2]
+        dimgs, dmats, ddepths = [], [None] * (2 * S), None
+        for i in reversed(range(S)):  # (autograd's order: the source swept last comes first)
+            want = (need[1], want_d, need[3 + 2 * i], need[4 + 2 * i])
+            if not any(want):
+                continue
+            src = psv_src_images[:, :, :, i * 3:(i + 1) * 3]
+            dimg, dde, dki, dproj = plane_sweep_backward(src, dd, mats[2 * i], mats[2 * i + 1],
+                                                         dout[..., 3 + i * D * 3:3 + (i + 1) * D * 3], want)
+            dimgs.insert(0, dimg)
+            if dde is not None:
+                ddepths = dde if ddepths is None else ddepths + dde
+            if dki is not None:
+                dmats[2 * i] = dki.reshape(ctx.shapes[1][2 * i])
+            if dproj is not None:
+                dmats[2 * i + 1] = dproj.reshape(ctx.shapes[1][2 * i + 1])
+        dsrc = torch.cat(dimgs, -1) if need[1] and S else None
+        if need[1] and dsrc is not None and dsrc.shape[-1] != psv_src_images.shape[-1]:
+            pad = torch.zeros(dsrc.shape[:-1] + (psv_src_images.shape[-1] - dsrc.shape[-1],), device=dsrc.device)
+            dsrc = torch.cat([dsrc, pad], -1)  # (channels beyond the S sources are not read)
+        if ddepths is not None:
+            ddepths = ddepths.reshape(ctx.shapes[0]).to(device=ctx.depths_on[0], dtype=ctx.depths_on[1])
+        return (dref, dsrc, ddepths, *dmats)
 
 
 # ---------------------------------------------------------------------------

@@ -26,6 +26,7 @@
 #include "render_bwd_cam.hip"
 #include "sweep.hip"
 #include "warp_bwd.hip"
+#include "psv_bwd.hip"
 #include "geometry.hip"
 #include "assemble.hip"
 #include "synth.hip"
@@ -1988,6 +1989,128 @@ int mpiv_inverse_warp_backward(const float* img, const int64_t st[4], int B, int
         warp_bwd_gather_kernel<<<dim3(blocks(ntex, 256), B, 1), 256, 0, q>>>(ws.key[cur], ws.id[cur], ws.pos, dout, ds, sp,
                                                                             make_fastdiv((unsigned)Wt), dimg);
     }
+    return launched(nm);
+}
+
+// The workspace of mpiv_plane_sweep_backward for groups of G planes: warp_bwd_layout's arrays for the B*G
+// (view, depth) pairs of a group and their bucket bounds table, then the partials of all D depths (not a
+// group's: the sums over them must not depend on the grouping), each part 256-byte aligned.
+static size_t psv_bwd_layout(int B, int G, int D, int64_t n, int64_t nb, PsvBwdWs* ws, char* base) {
+    const size_t nblk = (size_t)((n + kWarpThreads - 1) / kWarpThreads);
+    const size_t pairs = (size_t)B * G;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base ? base + off : nullptr;
+        off += (bytes + 255) & ~(size_t)255;
+        return p;
+    };
+    char* part = take((size_t)B * D * nblk * kPsvCam * 4);
+    char* pos = take(pairs * n * sizeof(float2));
+    char* k0 = take(pairs * n * 4);
+    char* k1 = take(pairs * n * 4);
+    char* i0 = take(pairs * n * 4);
+    char* i1 = take(pairs * n * 4);
+    char* hist = take(pairs * 256 * nblk * 4);
+    char* tot = take(pairs * 256 * 4);
+    char* table = take(pairs * nb * sizeof(uint2));
+    if (ws) {
+        ws->partials = reinterpret_cast<float*>(part);
+        ws->pos = reinterpret_cast<float2*>(pos);
+        ws->key[0] = reinterpret_cast<unsigned*>(k0);
+        ws->key[1] = reinterpret_cast<unsigned*>(k1);
+        ws->id[0] = reinterpret_cast<unsigned*>(i0);
+        ws->id[1] = reinterpret_cast<unsigned*>(i1);
+        ws->hist = reinterpret_cast<unsigned*>(hist);
+        ws->totals = reinterpret_cast<unsigned*>(tot);
+        ws->table = reinterpret_cast<uint2*>(table);
+    }
+    return off;
+}
+
+// the inverse warp's limits (31-bit pixel ids and keys), a channel index d*C+c and a count of partial
+// records B*D*nblk that stay 31-bit, and B views within the grid's y limit
+static bool psv_bwd_too_large(int B, int Hs, int Ws, int C, int Ht, int Wt, int D) {
+    if (warp_bwd_too_large(Hs, Ws, Ht, Wt) || B > kMaxGridYZ || (int64_t)D * C >= ((int64_t)1 << 31)) return true;
+    const int64_t nblk = ((int64_t)Ht * Wt + kWarpThreads - 1) / kWarpThreads;
+    return (int64_t)B * D >= ((int64_t)1 << 31) / nblk;
+}
+
+// the largest plane group: all D planes, as far as B*G stays within the grid's y limit
+static int psv_bwd_max_group(int B, int D) { return (int)std::min<int64_t>(D, kMaxGridYZ / B); }
+
+size_t mpiv_plane_sweep_backward_workspace_size(int B, int Hs, int Ws, int C, int Ht, int Wt, int D) {
+    if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0 || D <= 0 ||
+        psv_bwd_too_large(B, Hs, Ws, C, Ht, Wt, D))
+        return 0;
+    return psv_bwd_layout(B, psv_bwd_max_group(B, D), D, (int64_t)Ht * Wt, (int64_t)(Hs + 1) * (Ws + 1), nullptr, nullptr);
+}
+
+size_t mpiv_plane_sweep_backward_workspace_size_min(int B, int Hs, int Ws, int C, int Ht, int Wt, int D) {
+    if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0 || D <= 0 ||
+        psv_bwd_too_large(B, Hs, Ws, C, Ht, Wt, D))
+        return 0;
+    return psv_bwd_layout(B, 1, D, (int64_t)Ht * Wt, (int64_t)(Hs + 1) * (Ws + 1), nullptr, nullptr);
+}
+
+int mpiv_plane_sweep_backward(const float* img, const int64_t st[4], int B, int Hs, int Ws, int C, const float* ki,
+                              const float* proj, const float* depths, int D, int Ht, int Wt, const float* dout,
+                              const int64_t dost[4], float* dimg, float* ddepths, float* dki, float* dproj,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    const char* nm = "mpiv_plane_sweep_backward";
+    if (!img || !st || !ki || !proj || !depths || !dout || !dost || !workspace)
+        return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (!dimg && !ddepths && !dki && !dproj) return fail(MPIV_ERR_ARG, "%s: no gradient requested", nm);
+    if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if (D <= 0) return fail(MPIV_ERR_ARG, "%s: D must be positive", nm);
+    if (psv_bwd_too_large(B, Hs, Ws, C, Ht, Wt, D))
+        return fail(MPIV_ERR_ARG, "%s: one view is limited to Ht*Wt < 2^31 pixels and (Hs+1)*(Ws+1) < 2^31 buckets "
+                    "(the sort's key width), the volume to D*C < 2^31 channels and B*D*ceil(Ht*Wt/256) < 2^31 "
+                    "partial sums, the batch to 65535 views", nm);
+    const int64_t n = (int64_t)Ht * Wt, ntex = (int64_t)Hs * Ws, nbk = (int64_t)(Hs + 1) * (Ws + 1);
+    const size_t need = psv_bwd_layout(B, 1, D, n, nbk, nullptr, nullptr);
+    if (!aligned16(workspace) || workspace_bytes < need)
+        return fail(MPIV_ERR_ARG, "%s: workspace must be 16-byte aligned and hold at least %zu bytes "
+                    "(mpiv_plane_sweep_backward_workspace_size_min)", nm, need);
+    int G = psv_bwd_max_group(B, D);  // the largest group that fits
+    while (G > 1 && psv_bwd_layout(B, G, D, n, nbk, nullptr, nullptr) > workspace_bytes) --G;
+    PsvBwdWs ws;
+    psv_bwd_layout(B, G, D, n, nbk, &ws, static_cast<char*>(workspace));
+    hipStream_t q = S(stream);
+    const SweepParams sp = sweep_params(B, Hs, Ws, C, D, Ht, Wt);
+    const ImgStrides s{st[0], st[1], st[2], st[3]}, ds{dost[0], dost[1], dost[2], dost[3]};
+    const unsigned nblk = blocks(n, kWarpThreads);
+    const bool sums = ddepths || dki || dproj;
+    if (!dimg) {  // no sort: the pixel pass takes all planes at once
+        psv_bwd_pixel_kernel<<<dim3(nblk, B, 1), kWarpThreads, 0, q>>>(img, s, sp, ki, proj, depths, 0, D, dout, ds, nullptr,
+                                                                      nullptr, ws.partials, nblk);
+    } else {
+        int bits = 0;  // of the largest key, the "no bucket" id (Hs+1)*(Ws+1)
+        while (nbk >> bits) ++bits;
+        const int passes = (bits + 7) / 8;
+        const FastDiv fd_wt = make_fastdiv((unsigned)Wt);
+        for (int hi = D; hi > 0;) {  // plane groups in descending d
+            const int g = std::min(G, hi), d0 = hi - g;
+            const unsigned pairs = (unsigned)(B * g);
+            psv_bwd_pixel_kernel<<<dim3(nblk, B, 1), kWarpThreads, 0, q>>>(
+                img, s, sp, ki, proj, depths, d0, g, dout, ds, ws.pos, ws.key[0], sums ? ws.partials : nullptr, nblk);
+            int cur = 0;
+            for (int p = 0; p < passes; ++p, cur ^= 1) {
+                warp_sort_hist_kernel<<<dim3(nblk, pairs, 1), kWarpThreads, 0, q>>>(ws.key[cur], (unsigned)n, nblk, 8 * p,
+                                                                                   ws.hist);
+                warp_sort_scan_kernel<<<dim3(256, pairs, 1), 256, 0, q>>>(ws.hist, nblk, ws.totals);
+                warp_sort_scatter_kernel<<<dim3(nblk, pairs, 1), kWarpThreads, 0, q>>>(
+                    ws.key[cur], p == 0 ? nullptr : ws.id[cur], ws.key[cur ^ 1], ws.id[cur ^ 1], ws.hist, ws.totals,
+                    (unsigned)n, nblk, 8 * p);
+            }
+            psv_bwd_clear_kernel<<<dim3(blocks(nbk, 256), pairs, 1), 256, 0, q>>>(ws.table, (unsigned)nbk);
+            psv_bwd_bounds_kernel<<<dim3(nblk, pairs, 1), 256, 0, q>>>(ws.key[cur], (unsigned)n, (unsigned)nbk, ws.table);
+            psv_bwd_gather_kernel<<<dim3(blocks(ntex, 256), B, 1), 256, 0, q>>>(ws.id[cur], ws.pos, ws.table, dout, ds, sp,
+                                                                               fd_wt, d0, g, hi == D ? 1 : 0, dimg);
+            hi = d0;
+        }
+    }
+    if (dki || dproj) psv_bwd_cam_sum_kernel<<<B, 256, 0, q>>>(ws.partials, nblk, D, dki, dproj);
+    if (ddepths) psv_bwd_depth_sum_kernel<<<D, 256, 0, q>>>(ws.partials, nblk, B, D, ddepths);
     return launched(nm);
 }
 

@@ -386,13 +386,18 @@ def projective_inverse_warp_torch(img, depth, pose, intrinsics, ret_flows=False)
 
 def plane_sweep_torch(img, depth_planes, pose, intrinsics):
     """Plane-sweep volume [B, H, W, D*C] (channel d*C+c) of img [B, H, W, C] at the
-    listed depths (utils.py:452-471).  One HIP launch writes the whole volume."""
+    listed depths (utils.py:452-471).  One HIP launch writes the whole volume.  When img, pose,
+    intrinsics or a depth_planes tensor requires grad (grad enabled, img on the device) the volume is
+    differentiable w.r.t. them, as in the reference: one HIP adjoint call (psv_bwd.hip), d img bit-exact
+    to the reference's CPU autograd; the same holds for plane_sweep_torch_one / _one2."""
     batch, height, width, _ = img.shape
     return _plane_sweep(img, depth_planes, pose, intrinsics, intrinsics, height, width)
 
 
 def _plane_sweep(img, depth_planes, pose, src_intrinsics, tgt_intrinsics, height, width, B=None):
     """B given (the unbatched _one calls): img [Hs,Ws,C] and pose [4,4] stand for a batch of 1."""
+    if _warp_grad(img, depth_planes, pose, src_intrinsics, tgt_intrinsics):
+        return _plane_sweep_autograd(img, depth_planes, pose, src_intrinsics, tgt_intrinsics, height, width, B)
     if img.is_cuda and pose.is_cuda:  # pose in HBM: proj is formed there, in the sweep's own call
         dev = pose.device
         if B is None:
@@ -405,6 +410,25 @@ def _plane_sweep(img, depth_planes, pose, src_intrinsics, tgt_intrinsics, height
         img, pose = img.unsqueeze(0), pose.unsqueeze(0)
     ki, proj = _host.psv_matrices(_batched(src_intrinsics), _batched(tgt_intrinsics), pose, pin=img.is_cuda)
     return _lib.plane_sweep(img, depth_planes, ki, proj, height, width)
+
+
+def _plane_sweep_autograd(img, depth_planes, pose, src_intrinsics, tgt_intrinsics, height, width, B):
+    """The sweep as a node of the autograd graph (_lib.PlaneSweepFunction): mpiv_plane_sweep's launch and bits,
+    gradients for img, a depth_planes tensor, pose and the intrinsics.  The matrices come from the no-grad
+    routes unless a camera input requires grad; then from _host.psv_matrices_autograd's chain on the host
+    (not capturable)."""
+    _lib._require_depths(depth_planes)
+    if B is not None:
+        img, pose = img.unsqueeze(0), pose.unsqueeze(0)
+    if any(t.requires_grad for t in (pose, src_intrinsics, tgt_intrinsics)):
+        ki, proj = _host.psv_matrices_autograd(_batched(src_intrinsics), _batched(tgt_intrinsics), pose)
+        ki, proj = ki.to(img.device), proj.to(img.device)
+    elif pose.is_cuda:
+        ki, proj = _host.psv_matrices_device(src_intrinsics, tgt_intrinsics, pose, pose.shape[0])
+    else:
+        ki, proj = _host.psv_matrices(_batched(src_intrinsics), _batched(tgt_intrinsics), pose, pin=True)
+    depths = depth_planes if isinstance(depth_planes, torch.Tensor) else _lib._depths_on(depth_planes, img.device)
+    return _lib.PlaneSweepFunction.apply(img, depths, ki, proj, height, width)
 
 
 def _batched(k):
@@ -440,11 +464,39 @@ def format_network_input_torch(self, ref_image, psv_src_images, ref_pose, psv_sr
     """Network input [B, H, W, 3 + S*D*3]: the reference image followed by one plane-sweep
     volume per extra source (utils.py:473-498; the unused leading `self` is kept).
     Each source's volume is swept straight into its channel slice of the output
-    (no per-source tensors, no torch.cat)."""
+    (no per-source tensors, no torch.cat).  When ref_image, psv_src_images, a pose, the intrinsics or a
+    planes tensor requires grad (grad enabled, images on the device) the result is differentiable w.r.t.
+    them (_lib.NetworkInputFunction): each source's slice gets the sweep's adjoint of its own channel slice
+    of the gradient, read in place; the relative poses and the matrices then stay on the host graph."""
     S = psv_src_poses.shape[1]
+    if S and _warp_grad(ref_image, planes, psv_src_images, ref_pose, psv_src_poses, intrinsics) and psv_src_images.is_cuda:
+        return _network_input_autograd(ref_image, psv_src_images, ref_pose, psv_src_poses, planes, intrinsics)
     inv_ref = torch.inverse(_host._cpu32(ref_pose))
     rel = [torch.matmul(_host._cpu32(psv_src_poses[:, i]), inv_ref) for i in range(S)]  # utils.py:493
     return _lib.network_input(ref_image, psv_src_images, rel, planes, intrinsics)
+
+
+def _network_input_autograd(ref_image, psv_src_images, ref_pose, psv_src_poses, planes, intrinsics):
+    _lib._require_depths(planes)
+    dev = ref_image.device
+    S = psv_src_poses.shape[1]
+    cams = any(t.requires_grad for t in (ref_pose, psv_src_poses, intrinsics))
+    mats = []
+    if cams:  # utils.py:493 and the matrices as nodes of the host graph
+        host = lambda x: x.to(device="cpu", dtype=torch.float32)  # noqa: E731
+        _lib.host_under_capture("the plane sweep's camera chain (poses, intrinsics)")
+        poses = host(psv_src_poses)
+        for i in range(S):
+            rel = torch.matmul(poses[:, i], torch.inverse(host(ref_pose)))
+            ki, proj = _host.psv_matrices_autograd(intrinsics, intrinsics, rel)
+            mats += [ki.to(dev), proj.to(dev)]
+    else:
+        inv_ref = torch.inverse(_host._cpu32(ref_pose))
+        for i in range(S):
+            rel = torch.matmul(_host._cpu32(psv_src_poses[:, i]), inv_ref)
+            mats += list(_host.psv_matrices(intrinsics, intrinsics, rel, pin=True))
+    depths = planes if isinstance(planes, torch.Tensor) else _lib._depths_on(planes, dev)
+    return _lib.NetworkInputFunction.apply(ref_image, psv_src_images, depths, *mats)
 
 
 def plane_sweep_torch_one(img, depth_planes, pose, intrinsics):
