@@ -456,6 +456,38 @@ int mpiv_grid_sample(const float *in, const int64_t in_strides[4], int N, int C,
 int mpiv_over_composite(const float *const *layers, int P, int64_t n, int64_t pixel_stride,
                         int64_t channel_stride, float *out, void *stream);
 
+/* The adjoint of mpiv_grid_sample (helper_bwd.hip): gradients of sum(out * dout) w.r.t. the input and
+ * the coordinates, ATen's CPU grid_sampler_2d_backward order and bits (zeros' signs and the non-finite
+ * pattern included).
+ * in, coords: the forward's arguments, read by their element strides
+ * dout:    element strides dout_strides[4] in (N,C,H,W) order (any, stride 0 included)
+ * din:     [N,Hi,Wi,C] contiguous (channels last), every texel written; dcoords: [N,Ho,Wo,2] contiguous.
+ *          NULL for a gradient that is not wanted (at least one is); only the kernels the wanted
+ *          gradients need are launched.
+ * d input is mpiv_inverse_warp_backward's sort and gather over the positions of `coords`.  workspace:
+ * 16-byte aligned, at least mpiv_grid_sample_backward_workspace_size bytes (0: a size the kernels cannot
+ * index, Ho*Wo or (Hi+1)*(Wi+1) >= 2^31, which the entry refuses); not read when din is NULL (may be NULL
+ * then).  No allocation, no synchronisation and no float atomics inside. */
+size_t mpiv_grid_sample_backward_workspace_size(int N, int C, int Hi, int Wi, int Ho, int Wo);
+int mpiv_grid_sample_backward(const float *in, const int64_t in_strides[4], int N, int C, int Hi, int Wi,
+                              const float *coords, const int64_t coord_strides[4], int Ho, int Wo,
+                              const float *dout, const int64_t dout_strides[4], float *din, float *dcoords,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* The adjoint of mpiv_over_composite (helper_bwd.hip), the reference's CPU autograd bits.
+ * layers:  the forward's DEVICE pointer table and strides
+ * dout:    [n][3] with element strides dout_strides[2] = (pixel, channel), stride 0 included
+ * dlayers: [P][n][4] contiguous; layer 0's alpha gradient is +0.  16-B loads and stores are taken when
+ *          channel_stride == 1, pixel_stride == 4 and the pointers are 16-byte aligned.
+ * workspace: 16-byte aligned, at least mpiv_over_composite_backward_workspace_size bytes: the composite
+ *          before every chunk of 8 layers but the first, 12 B per pixel and chunk (0 for P <= 9, where it
+ *          may be NULL, and for n >= 2^31, which the entry refuses).  No allocation and no
+ *          synchronisation inside. */
+size_t mpiv_over_composite_backward_workspace_size(int P, int64_t n);
+int mpiv_over_composite_backward(const float *const *layers, int P, int64_t n, int64_t pixel_stride,
+                                 int64_t channel_stride, const float *dout, const int64_t dout_strides[2],
+                                 float *dlayers, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- geometry helpers ---------------------------------------------------- */
 
 /* transform_points_torch (utils.py:69-88): pts [M][n][3], homs [M][9] -> out [M][n][3] */

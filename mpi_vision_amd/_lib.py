@@ -126,7 +126,15 @@ _SIGS_PSV = {
     "mpiv_plane_sweep_backward": [_vp, _c_i64p, _int, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp,
                                   _c_i64p, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp],
 }
-EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_F16_TRAIN) + tuple(_SIGS_WARP) + tuple(_SIGS_PSV) + (
+# the sampler's and the compositor's adjoints (helper_bwd.hip): on their own for the same reason; their
+# side-stream and graph-replay cases are in tests/test_helpergrad_gpu.py.
+_SIGS_HELPER_BWD = {
+    "mpiv_grid_sample_backward": [_vp, _c_i64p, _int, _int, _int, _int, _vp, _c_i64p, _int, _int, _vp, _c_i64p, _vp,
+                                  _vp, _vp, ctypes.c_size_t, _vp],
+    "mpiv_over_composite_backward": [_vp, _int, _i64, _i64, _i64, _vp, _c_i64p, _vp, _vp, ctypes.c_size_t, _vp],
+}
+EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_F16_TRAIN) + tuple(_SIGS_WARP) + tuple(_SIGS_PSV) + tuple(_SIGS_HELPER_BWD) + (
+                          "mpiv_grid_sample_backward_workspace_size", "mpiv_over_composite_backward_workspace_size",
                           "mpiv_plane_sweep_backward_workspace_size", "mpiv_plane_sweep_backward_workspace_size_min",
                           "mpiv_inverse_warp_backward_workspace_size","mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
                           "mpiv_render_backward_abort_flag",
@@ -191,7 +199,7 @@ def _open(path: str, check_id: bool):
     L.mpiv_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int]
     L.mpiv_debug_set.restype = ctypes.c_int
     for name, args in (*_SIGS.items(), *_SIGS_CAM.items(), *_SIGS_ALPHA.items(), *_SIGS_F16_TRAIN.items(),
-                       *_SIGS_WARP.items(), *_SIGS_PSV.items()):
+                       *_SIGS_WARP.items(), *_SIGS_PSV.items(), *_SIGS_HELPER_BWD.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int
@@ -209,6 +217,10 @@ def _open(path: str, check_id: bool):
     for fn in (L.mpiv_plane_sweep_backward_workspace_size, L.mpiv_plane_sweep_backward_workspace_size_min):
         fn.argtypes = [_int] * 7
         fn.restype = ctypes.c_size_t
+    L.mpiv_grid_sample_backward_workspace_size.argtypes = [_int] * 6
+    L.mpiv_grid_sample_backward_workspace_size.restype = ctypes.c_size_t
+    L.mpiv_over_composite_backward_workspace_size.argtypes = [_int, _i64]
+    L.mpiv_over_composite_backward_workspace_size.restype = ctypes.c_size_t
     L.mpiv_render_backward_abort_flag.argtypes = [_int]
     L.mpiv_render_backward_abort_flag.restype = ctypes.c_void_p
     if L.mpiv_abi_version() != ABI_VERSION:
@@ -1684,10 +1696,8 @@ class NetworkInputFunction(torch.autograd.Function):
 # sampler / compositor primitives
 # ---------------------------------------------------------------------------
 
-def bilinear_sample(imgs: torch.Tensor, coords: torch.Tensor, channels_last_out: bool) -> torch.Tensor:
-    """channels_last_out=False: bilinear_wrapper_torch semantics ([..., Hs, Ws, C] ->
-    [..., C, Ht, Wt]); True: resampler_wrapper_torch ([N,H,W,C] -> [N,H',W',C])."""
-    dev = _dev(imgs, coords)
+def _sample_args(imgs: torch.Tensor, coords: torch.Tensor, channels_last_out: bool):
+    """(im4 [N,Hi,Wi,C], co4 [N,Ho,Wo,2], lead dims) of a sampler call."""
     if channels_last_out:
         if imgs.dim() != 4 or coords.dim() != 4:
             raise RuntimeError("resampler_wrapper_torch expects imgs [N,H,W,C] and coords [N,H,W,2]")
@@ -1701,9 +1711,15 @@ def bilinear_sample(imgs: torch.Tensor, coords: torch.Tensor, channels_last_out:
             n *= s
         im4 = imgs.reshape([n] + list(imgs.shape[-3:]))
         co4 = coords.reshape([n] + list(coords.shape[-3:]))
-    N, Hi, Wi, C = im4.shape
-    if co4.shape[0] != N or co4.shape[-1] != 2:
+    if co4.shape[0] != im4.shape[0] or co4.shape[-1] != 2:
         raise RuntimeError(f"grid_sample: coords {tuple(coords.shape)} do not match images {tuple(imgs.shape)}")
+    return im4, co4, lead
+
+
+def _bilinear_sample(imgs: torch.Tensor, coords: torch.Tensor, channels_last_out: bool) -> torch.Tensor:
+    dev = _dev(imgs, coords)
+    im4, co4, lead = _sample_args(imgs, coords, channels_last_out)
+    N, Hi, Wi, C = im4.shape
     Ho, Wo = co4.shape[1], co4.shape[2]
     if channels_last_out:
         out = torch.empty((N, Ho, Wo, C), device=dev, dtype=torch.float32)
@@ -1718,6 +1734,67 @@ def bilinear_sample(imgs: torch.Tensor, coords: torch.Tensor, channels_last_out:
     return out.reshape(lead + [C, Ho, Wo])
 
 
+def bilinear_sample(imgs: torch.Tensor, coords: torch.Tensor, channels_last_out: bool) -> torch.Tensor:
+    """channels_last_out=False: bilinear_wrapper_torch semantics ([..., Hs, Ws, C] ->
+    [..., C, Ht, Wt]); True: resampler_wrapper_torch ([N,H,W,C] -> [N,H',W',C]).  Differentiable w.r.t.
+    imgs and coords (GridSampleFunction) when either requires grad; otherwise the plain launch."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (imgs, coords)):
+        return GridSampleFunction.apply(imgs, coords, channels_last_out)
+    return _bilinear_sample(imgs, coords, channels_last_out)
+
+
+def grid_sample_backward(imgs, coords, dout, channels_last_out: bool, want=(True, True), workspace=None):
+    """The adjoint of bilinear_sample (mpiv_grid_sample_backward, helper_bwd.hip): for dout in the
+    forward's output shape (read by its element strides: a stride-0 or permuted gradient of 4-d inputs is
+    not copied) returns (d imgs in imgs' shape, d coords in coords' shape), None where `want` says so;
+    ATen's CPU grid_sampler_2d_backward bits.  One call on the current stream; the workspace
+    (mpiv_grid_sample_backward_workspace_size bytes, for d imgs only) is the caller's or a torch.empty on
+    the same stream."""
+    dev = _dev(imgs, coords, dout)
+    im4, co4, lead = _sample_args(imgs, coords, channels_last_out)
+    N, Hi, Wi, C = im4.shape
+    Ho, Wo = co4.shape[1], co4.shape[2]
+    oshape = [N, Ho, Wo, C] if channels_last_out else lead + [C, Ho, Wo]
+    if list(dout.shape) != oshape:
+        raise RuntimeError(f"grad_output must be {oshape}, got {list(dout.shape)}")
+    if not any(want):
+        raise RuntimeError("grid_sample_backward: nothing to compute")
+    if channels_last_out:
+        dst = _strides(dout, (0, 3, 1, 2))
+    else:
+        dout = dout.reshape(N, C, Ho, Wo)
+        dst = _strides(dout)
+    ws = None
+    if want[0]:
+        need = load().mpiv_grid_sample_backward_workspace_size(N, C, Hi, Wi, Ho, Wo)
+        ws = workspace if workspace is not None else torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev:
+            raise RuntimeError(f"workspace must be a contiguous uint8 tensor on {dev}")
+    din = torch.empty((N, Hi, Wi, C), device=dev, dtype=torch.float32) if want[0] else None
+    dco = torch.empty((N, Ho, Wo, 2), device=dev, dtype=torch.float32) if want[1] else None
+    _call("mpiv_grid_sample_backward", im4, _strides(im4, (0, 3, 1, 2)), N, C, Hi, Wi, co4, _strides(co4), Ho, Wo,
+          dout, dst, din, dco, ws, ws.numel() if ws is not None else 0, _stream(dev))
+    return (din.reshape(imgs.shape) if want[0] else None), (dco.reshape(coords.shape) if want[1] else None)
+
+
+class GridSampleFunction(torch.autograd.Function):
+    """Autograd node of the sampler: forward = the plain mpiv_grid_sample launch (the same bits as the
+    no-grad call), backward = grid_sample_backward() w.r.t. whichever of imgs and coords require grad."""
+
+    @staticmethod
+    def forward(ctx, imgs, coords, channels_last_out):
+        ctx.save_for_backward(imgs, coords)
+        ctx.channels_last_out = channels_last_out
+        return _bilinear_sample(imgs, coords, channels_last_out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        imgs, coords = ctx.saved_tensors
+        dimgs, dcoords = grid_sample_backward(imgs, coords, dout, ctx.channels_last_out, ctx.needs_input_grad[:2])
+        return dimgs, dcoords, None
+
+
 def _flat_pixels(t: torch.Tensor):
     """(pixel_stride, channel_stride) if the leading dims of t [..., 4] collapse to one
     uniform pixel stride, else None."""
@@ -1730,11 +1807,13 @@ def _flat_pixels(t: torch.Tensor):
     return ps, t.stride(-1)
 
 
-def over_composite(rgbas) -> torch.Tensor:
+def _over_layers(rgbas):
+    """(layers, pixel stride, channel stride, n, shape) of an over_composite call: the layers as they
+    are when one stride pair describes them all, else contiguous copies."""
     rgbas = list(rgbas)
     if not rgbas:
         raise UnboundLocalError("over_composite: empty list")  # the reference fails the same way
-    dev = _dev(*rgbas)
+    _dev(*rgbas)
     shape = rgbas[0].shape
     if shape[-1] != 4:
         raise RuntimeError(f"over_composite expects RGBA layers, got {tuple(shape)}")
@@ -1747,7 +1826,12 @@ def over_composite(rgbas) -> torch.Tensor:
     if None in {_flat_pixels(t) for t in layers} or len({_flat_pixels(t) for t in layers}) != 1:
         layers = [t.contiguous() for t in layers]
     ps, cs = _flat_pixels(layers[0])
-    n = layers[0].numel() // 4
+    return layers, ps, cs, layers[0].numel() // 4, shape
+
+
+def _over_composite(rgbas) -> torch.Tensor:
+    layers, ps, cs, n, shape = _over_layers(rgbas)
+    dev = layers[0].device
     host_under_capture("over_composite's layer pointer table (built on the host per call)")
     ptrs = torch.tensor([t.data_ptr() for t in layers], dtype=torch.int64).to(dev)
     out = torch.empty(tuple(shape[:-1]) + (3,), device=dev, dtype=torch.float32)
@@ -1755,6 +1839,60 @@ def over_composite(rgbas) -> torch.Tensor:
     # temporaries (pointer table, contiguous copies) may be freed now: the caching
     # allocator only hands their memory to later work on this same stream
     return out
+
+
+def over_composite(rgbas) -> torch.Tensor:
+    """over_composite (utils.py:136-157).  Differentiable w.r.t. every layer (OverCompositeFunction)
+    when one requires grad; otherwise the plain launch."""
+    rgbas = list(rgbas)
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in rgbas):
+        return OverCompositeFunction.apply(*rgbas)
+    return _over_composite(rgbas)
+
+
+def over_composite_backward(rgbas, dout, workspace=None) -> torch.Tensor:
+    """The adjoint of over_composite (mpiv_over_composite_backward, helper_bwd.hip): d layers as one
+    [P, ..., 4] block, the reference's CPU autograd bits.  dout [..., 3] is read by its strides where its
+    leading dims collapse to one pixel stride (stride 0 included), else copied.  One call on the current
+    stream; the workspace (mpiv_over_composite_backward_workspace_size bytes) is the caller's or a
+    torch.empty on the same stream."""
+    layers, ps, cs, n, shape = _over_layers(rgbas)
+    dev = _dev(dout, *layers)
+    if tuple(dout.shape) != tuple(shape[:-1]) + (3,):
+        raise RuntimeError(f"grad_output must be {tuple(shape[:-1]) + (3,)}, got {tuple(dout.shape)}")
+    if _flat_pixels(dout) is None:
+        dout = dout.contiguous()
+    P = len(layers)
+    need = load().mpiv_over_composite_backward_workspace_size(P, n)
+    ws = workspace  # (P <= 9 needs none)
+    if ws is None and need:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    if ws is not None and (ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.device != dev):
+        raise RuntimeError(f"workspace must be a contiguous uint8 tensor on {dev}")
+    host_under_capture("over_composite's layer pointer table (built on the host per call)")
+    ptrs = torch.tensor([t.data_ptr() for t in layers], dtype=torch.int64).to(dev)
+    dlayers = torch.empty((P,) + tuple(shape), device=dev, dtype=torch.float32)
+    dst = (ctypes.c_int64 * 2)(*_flat_pixels(dout))
+    _call("mpiv_over_composite_backward", ptrs, P, n, ps, cs, dout, dst, dlayers, ws,
+          ws.numel() if ws is not None else 0, _stream(dev))
+    return dlayers
+
+
+class OverCompositeFunction(torch.autograd.Function):
+    """Autograd node of over_composite(*layers): forward = the plain mpiv_over_composite launch,
+    backward = over_composite_backward(); the per-layer gradients are views of its one block (layers that
+    are views of one tensor, or one tensor listed twice, accumulate through autograd as usual)."""
+
+    @staticmethod
+    def forward(ctx, *layers):
+        ctx.save_for_backward(*layers)
+        return _over_composite(layers)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        dlayers = over_composite_backward(ctx.saved_tensors, dout)
+        return tuple(dlayers[p] if need else None for p, need in enumerate(ctx.needs_input_grad))
 
 
 # ---------------------------------------------------------------------------

@@ -27,6 +27,7 @@
 #include "sweep.hip"
 #include "warp_bwd.hip"
 #include "psv_bwd.hip"
+#include "helper_bwd.hip"
 #include "geometry.hip"
 #include "assemble.hip"
 #include "synth.hip"
@@ -1942,6 +1943,25 @@ static bool warp_bwd_too_large(int Hs, int Ws, int Ht, int Wt) {
     return (int64_t)Ht * Wt >= ((int64_t)1 << 31) || (int64_t)(Hs + 1) * (Ws + 1) >= ((int64_t)1 << 31);
 }
 
+// The stable LSD radix sort of the pixel ids of `views` views of n pixels by bucket key (key[0] holds the
+// keys; nbk, the "no bucket" id, is the largest): 8 bits per pass, each pass a histogram, a scan and a
+// scatter between the ping-pong arrays.  Returns which of key[] / id[] holds the sorted result.
+static int warp_sort_launch(unsigned* const key[2], unsigned* const id[2], unsigned* hist, unsigned* totals,
+                            unsigned views, int64_t n, int64_t nbk, hipStream_t q) {
+    const unsigned nblk = blocks(n, kWarpThreads);
+    int bits = 0;  // of the largest key
+    while (nbk >> bits) ++bits;
+    const int passes = (bits + 7) / 8;
+    int cur = 0;
+    for (int p = 0; p < passes; ++p, cur ^= 1) {
+        warp_sort_hist_kernel<<<dim3(nblk, views, 1), kWarpThreads, 0, q>>>(key[cur], (unsigned)n, nblk, 8 * p, hist);
+        warp_sort_scan_kernel<<<dim3(256, views, 1), 256, 0, q>>>(hist, nblk, totals);
+        warp_sort_scatter_kernel<<<dim3(nblk, views, 1), kWarpThreads, 0, q>>>(
+            key[cur], p == 0 ? nullptr : id[cur], key[cur ^ 1], id[cur ^ 1], hist, totals, (unsigned)n, nblk, 8 * p);
+    }
+    return cur;
+}
+
 size_t mpiv_inverse_warp_backward_workspace_size(int B, int Hs, int Ws, int C, int Ht, int Wt) {
     if (B <= 0 || Hs <= 0 || Ws <= 0 || C <= 0 || Ht <= 0 || Wt <= 0 || warp_bwd_too_large(Hs, Ws, Ht, Wt)) return 0;
     return warp_bwd_layout(B, (int64_t)Ht * Wt, nullptr, nullptr);
@@ -1976,16 +1996,7 @@ int mpiv_inverse_warp_backward(const float* img, const int64_t st[4], int B, int
         dimg ? ws.key[0] : nullptr, cam ? ws.partials : nullptr, nblk);
     if (cam) warp_bwd_cam_sum_kernel<<<B, 256, 0, q>>>(ws.partials, nblk, dki, dproj);
     if (dimg) {
-        int bits = 0;  // of the largest key, the "no bucket" id (Hs+1)*(Ws+1)
-        while (((int64_t)(Hs + 1) * (Ws + 1)) >> bits) ++bits;
-        const int passes = (bits + 7) / 8;
-        int cur = 0;
-        for (int p = 0; p < passes; ++p, cur ^= 1) {
-            warp_sort_hist_kernel<<<dim3(nblk, B, 1), kWarpThreads, 0, q>>>(ws.key[cur], (unsigned)n, nblk, 8 * p, ws.hist);
-            warp_sort_scan_kernel<<<dim3(256, B, 1), 256, 0, q>>>(ws.hist, nblk, ws.totals);
-            warp_sort_scatter_kernel<<<dim3(nblk, B, 1), kWarpThreads, 0, q>>>(
-                ws.key[cur], p == 0 ? nullptr : ws.id[cur], ws.key[cur ^ 1], ws.id[cur ^ 1], ws.hist, ws.totals, (unsigned)n, nblk, 8 * p);
-        }
+        const int cur = warp_sort_launch(ws.key, ws.id, ws.hist, ws.totals, (unsigned)B, n, (int64_t)(Hs + 1) * (Ws + 1), q);
         warp_bwd_gather_kernel<<<dim3(blocks(ntex, 256), B, 1), 256, 0, q>>>(ws.key[cur], ws.id[cur], ws.pos, dout, ds, sp,
                                                                             make_fastdiv((unsigned)Wt), dimg);
     }
@@ -2084,24 +2095,13 @@ int mpiv_plane_sweep_backward(const float* img, const int64_t st[4], int B, int 
         psv_bwd_pixel_kernel<<<dim3(nblk, B, 1), kWarpThreads, 0, q>>>(img, s, sp, ki, proj, depths, 0, D, dout, ds, nullptr,
                                                                       nullptr, ws.partials, nblk);
     } else {
-        int bits = 0;  // of the largest key, the "no bucket" id (Hs+1)*(Ws+1)
-        while (nbk >> bits) ++bits;
-        const int passes = (bits + 7) / 8;
         const FastDiv fd_wt = make_fastdiv((unsigned)Wt);
         for (int hi = D; hi > 0;) {  // plane groups in descending d
             const int g = std::min(G, hi), d0 = hi - g;
             const unsigned pairs = (unsigned)(B * g);
             psv_bwd_pixel_kernel<<<dim3(nblk, B, 1), kWarpThreads, 0, q>>>(
                 img, s, sp, ki, proj, depths, d0, g, dout, ds, ws.pos, ws.key[0], sums ? ws.partials : nullptr, nblk);
-            int cur = 0;
-            for (int p = 0; p < passes; ++p, cur ^= 1) {
-                warp_sort_hist_kernel<<<dim3(nblk, pairs, 1), kWarpThreads, 0, q>>>(ws.key[cur], (unsigned)n, nblk, 8 * p,
-                                                                                   ws.hist);
-                warp_sort_scan_kernel<<<dim3(256, pairs, 1), 256, 0, q>>>(ws.hist, nblk, ws.totals);
-                warp_sort_scatter_kernel<<<dim3(nblk, pairs, 1), kWarpThreads, 0, q>>>(
-                    ws.key[cur], p == 0 ? nullptr : ws.id[cur], ws.key[cur ^ 1], ws.id[cur ^ 1], ws.hist, ws.totals,
-                    (unsigned)n, nblk, 8 * p);
-            }
+            const int cur = warp_sort_launch(ws.key, ws.id, ws.hist, ws.totals, pairs, n, nbk, q);
             psv_bwd_clear_kernel<<<dim3(blocks(nbk, 256), pairs, 1), 256, 0, q>>>(ws.table, (unsigned)nbk);
             psv_bwd_bounds_kernel<<<dim3(nblk, pairs, 1), 256, 0, q>>>(ws.key[cur], (unsigned)n, (unsigned)nbk, ws.table);
             psv_bwd_gather_kernel<<<dim3(blocks(ntex, 256), B, 1), 256, 0, q>>>(ws.id[cur], ws.pos, ws.table, dout, ds, sp,
@@ -2136,6 +2136,80 @@ int mpiv_over_composite(const float* const* layers, int P, int64_t n, int64_t ps
     if (P <= 0 || n <= 0) return fail(MPIV_ERR_ARG, "mpiv_over_composite: bad shape");
     over_composite_kernel<<<blocks(n, 256), 256, 0, S(stream)>>>(layers, P, n, ps, cs, out);
     return launched("mpiv_over_composite");
+}
+
+// The adjoint of mpiv_grid_sample: warp_bwd_layout's arrays (d input's positions, keys and sort; the
+// camera partials' share stays unused), so the two entries' workspaces are interchangeable.
+size_t mpiv_grid_sample_backward_workspace_size(int N, int C, int Hi, int Wi, int Ho, int Wo) {
+    if (N <= 0 || C <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0 || warp_bwd_too_large(Hi, Wi, Ho, Wo)) return 0;
+    return warp_bwd_layout(N, (int64_t)Ho * Wo, nullptr, nullptr);
+}
+
+int mpiv_grid_sample_backward(const float* in, const int64_t ist[4], int N, int C, int Hi, int Wi,
+                              const float* coords, const int64_t cst[4], int Ho, int Wo, const float* dout,
+                              const int64_t dost[4], float* din, float* dcoords, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    const char* nm = "mpiv_grid_sample_backward";
+    if (!in || !ist || !coords || !cst || !dout || !dost) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (!din && !dcoords) return fail(MPIV_ERR_ARG, "%s: no gradient requested", nm);
+    if (N <= 0 || C <= 0 || Hi <= 0 || Wi <= 0 || Ho <= 0 || Wo <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if (N > kMaxGridYZ) return fail(MPIV_ERR_ARG, "%s: too large", nm);
+    if (warp_bwd_too_large(Hi, Wi, Ho, Wo))
+        return fail(MPIV_ERR_ARG, "%s: one image is limited to Ho*Wo < 2^31 pixels and (Hi+1)*(Wi+1) < 2^31 buckets "
+                    "(the sort's key width)", nm);
+    const int64_t n = (int64_t)Ho * Wo, ntex = (int64_t)Hi * Wi;
+    WarpBwdWs ws{};
+    if (din) {  // (d coords alone needs no workspace)
+        const size_t need = warp_bwd_layout(N, n, &ws, static_cast<char*>(workspace));
+        if (!workspace || !aligned16(workspace) || workspace_bytes < need)
+            return fail(MPIV_ERR_ARG, "%s: workspace must be 16-byte aligned and hold %zu bytes "
+                        "(mpiv_grid_sample_backward_workspace_size)", nm, need);
+    }
+    hipStream_t q = S(stream);
+    const SweepParams sp = sweep_params(N, Hi, Wi, C, 1, Ho, Wo);
+    // (N,C,H,W) strides -> the NHWC order of ImgStrides; coords as mpiv_grid_sample reads them
+    const ImgStrides s{ist[0], ist[2], ist[3], ist[1]}, ds{dost[0], dost[2], dost[3], dost[1]};
+    const Strides4 cs{cst[0], cst[3], cst[1], cst[2]};
+    grid_bwd_pixel_kernel<<<dim3(blocks(n, kWarpThreads), N, 1), kWarpThreads, 0, q>>>(
+        in, s, sp, coords, cs, dout, ds, dcoords, din ? ws.pos : nullptr, din ? ws.key[0] : nullptr);
+    if (din) {
+        const int cur = warp_sort_launch(ws.key, ws.id, ws.hist, ws.totals, (unsigned)N, n, (int64_t)(Hi + 1) * (Wi + 1), q);
+        warp_bwd_gather_kernel<<<dim3(blocks(ntex, 256), N, 1), 256, 0, q>>>(ws.key[cur], ws.id[cur], ws.pos, dout, ds, sp,
+                                                                            make_fastdiv((unsigned)Wo), din);
+    }
+    return launched(nm);
+}
+
+// The adjoint of mpiv_over_composite: the colour before every chunk of kOverChunk layers but the first,
+// three floats per pixel and chunk.  0: P <= kOverChunk + 1 (no workspace), or a size the entry refuses
+// (the kernel's layer and chunk counts are ints, its grid one block per 256 pixels).
+static bool over_bwd_too_large(int P, int64_t n) { return n >= ((int64_t)1 << 31) || P >= (1 << 24); }
+
+size_t mpiv_over_composite_backward_workspace_size(int P, int64_t n) {
+    if (P <= 0 || n <= 0 || over_bwd_too_large(P, n)) return 0;
+    const int64_t nch = ((int64_t)P - 1 + kOverChunk - 1) / kOverChunk;
+    return nch <= 1 ? 0 : (size_t)(nch - 1) * 3 * (size_t)n * sizeof(float);
+}
+
+int mpiv_over_composite_backward(const float* const* layers, int P, int64_t n, int64_t ps, int64_t cs,
+                                 const float* dout, const int64_t dost[2], float* dlayers, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    const char* nm = "mpiv_over_composite_backward";
+    if (!layers || !dout || !dost || !dlayers) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
+    if (P <= 0 || n <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if (over_bwd_too_large(P, n)) return fail(MPIV_ERR_ARG, "%s: limited to n < 2^31 pixels and P < 2^24 layers", nm);
+    const size_t need = mpiv_over_composite_backward_workspace_size(P, n);
+    if (need && (!workspace || !aligned16(workspace) || workspace_bytes < need))
+        return fail(MPIV_ERR_ARG, "%s: workspace must be 16-byte aligned and hold %zu bytes "
+                    "(mpiv_over_composite_backward_workspace_size)", nm, need);
+    float* ck = static_cast<float*>(workspace);
+    // 16-B loads and stores: RGBA contiguous per pixel, pixels dense (a layer whose own pointer is not
+    // 16-byte aligned takes scalar loads inside the kernel)
+    if (ps == 4 && cs == 1 && aligned16(dlayers))
+        over_bwd_kernel<true><<<blocks(n, 256), 256, 0, S(stream)>>>(layers, P, n, ps, cs, dout, dost[0], dost[1], dlayers, ck);
+    else
+        over_bwd_kernel<false><<<blocks(n, 256), 256, 0, S(stream)>>>(layers, P, n, ps, cs, dout, dost[0], dost[1], dlayers, ck);
+    return launched(nm);
 }
 
 int mpiv_transform_points(const float* pts, int M, int64_t n, const float* homs, float* out, void* stream) {

@@ -89,31 +89,38 @@ def normalize_homogeneous_torch(points):
 def bilinear_wrapper_torch(imgs, coords):
     """grid_sample(bilinear, zeros, align_corners=False) of imgs [..., H_s, W_s, C] at
     coords [..., H_t, W_t, 2] in [0,1] (x first).  Returns [..., C, H_t, W_t] like the
-    reference (utils.py:104-134)."""
+    reference (utils.py:104-134).  Differentiable w.r.t. imgs and coords (HIP adjoint, ATen's CPU
+    grid_sampler_2d_backward bits); no double backward."""
     return _lib.bilinear_sample(imgs, coords, channels_last_out=False)
 
 
 def resampler_wrapper_torch(imgs, coords):
-    """grid_sample of NHWC imgs at coords [N, H', W', 2] -> [N, H', W', C] (utils.py:395-407)."""
+    """grid_sample of NHWC imgs at coords [N, H', W', 2] -> [N, H', W', C] (utils.py:395-407).
+    Differentiable w.r.t. imgs and coords, as bilinear_wrapper_torch."""
     return _lib.bilinear_sample(imgs, coords, channels_last_out=True)
 
 
 def over_composite(rgbas):
     """Back-to-front over-compositing of a list of [B,H,W,4] images; the first image's
-    alpha is ignored (utils.py:136-157)."""
+    alpha is ignored (utils.py:136-157).  Differentiable w.r.t. every layer (HIP adjoint, the
+    reference's CPU autograd bits); raises under a HIP-graph capture (host pointer table)."""
     return _lib.over_composite(rgbas)
 
 
 def transform_plane_imgs_torch(imgs, pixel_coords_trg, k_s, k_t, rot, t, n_hat, a):
     """Warp [..., H_s, W_s, C] plane images with per-plane homographies; returns
-    [..., C, H_t, W_t] (utils.py:160-195, including its x/(H-1), y/(W-1) normalisation)."""
+    [..., C, H_t, W_t] (utils.py:160-195, including its x/(H-1), y/(W-1) normalisation).
+    Differentiable w.r.t. imgs (the sampler's HIP adjoint).  The camera arguments (k_s, k_t, rot, t,
+    n_hat, a) and pixel_coords_trg are not differentiable here: for camera gradients use
+    mpi_render_view_torch."""
     hom = inv_homography_torch(k_s, k_t, rot, t, n_hat, a)
     return _lib.warp_planes(imgs, pixel_coords_trg, hom)
 
 
 def planar_transform_torch(imgs, pixel_coords_trg, k_s, k_t, rot, t, n_hat, a):
     """Layer-batched planar transform (utils.py:198-233): imgs [L, B, H, W, C],
-    per-batch cameras, per-layer planes -> [L, B, C, H_t, W_t]."""
+    per-batch cameras, per-layer planes -> [L, B, C, H_t, W_t].  Differentiable w.r.t. imgs only
+    (camera gradients: mpi_render_view_torch)."""
     n_layers = imgs.shape[0]
 
     def rep(x):
@@ -125,7 +132,8 @@ def planar_transform_torch(imgs, pixel_coords_trg, k_s, k_t, rot, t, n_hat, a):
 
 def projective_forward_homography_torch(src_images, intrinsics, pose, depths):
     """Forward-warp [L, B, H, W, C] layers to the target pose (utils.py:237-265);
-    returns [L, B, C, H, W]."""
+    returns [L, B, C, H, W].  Differentiable w.r.t. src_images only (camera gradients:
+    mpi_render_view_torch)."""
     n_layers, n_batch, height, width, _ = src_images.shape
     rot, t = pose[:, :3, :3], pose[:, :3, 3:]
     n_hat = torch.tensor([0.0, 0.0, 1.0], device=pose.device).reshape(1, 1, 1, 3)
