@@ -19,6 +19,14 @@
  *  - All arithmetic is fp32 and rounds exactly like the reference's ATen CPU
  *    ops; matrices (homographies, Ki, proj) are computed by the
  *    caller on the host and passed as device buffers.
+ *  - The fused frame kernels (render, inverse warp, plane sweep and their adjoints)
+ *    restate the reference's per-pixel matmuls as MKL sgemm rounds them, a chain of
+ *    fused multiply-adds.  ATen's CPU bmm hands a product to MKL only from 400
+ *    multiply-adds per batch element up (see "geometry helpers" below), so the render is
+ *    bit-exact to the reference from H*W >= 45 pixels, the inverse warp, the sweep and
+ *    their adjoints from Ht*Wt >= 45 target pixels (their cam2pixel step alone from 25;
+ *    pixel2cam from 45 for a general K).  On a smaller frame a sample position may
+ *    differ from the reference's in its last bit (DESIGN.md has the measured counts).
  */
 #ifndef MPIV_H
 #define MPIV_H
@@ -490,25 +498,42 @@ int mpiv_over_composite_backward(const float *const *layers, int P, int64_t n, i
 
 /* ---- geometry helpers ---------------------------------------------------- */
 
-/* transform_points_torch (utils.py:69-88): pts [M][n][3], homs [M][9] -> out [M][n][3] */
+/* The reference's torch.matmul rounds the four products below in one of two ways.  ATen's CPU bmm runs a
+ * naive loop when contraction * rows * cols < 400 per batch element: plain products summed in ascending k,
+ * every product and partial sum rounded.  Larger products go to MKL sgemm: a chain of fused multiply-adds
+ * in ascending k, fma(a2, x2, fma(a1, x1, a0 * x0)).  For the 3x3 products (transform_points, plane_coords,
+ * pixel2cam) the naive loop runs up to n = 44 points per batch element, for cam2pixel's 4x4 up to n = 24.
+ * Each entry has two forms: the one without a `plain` argument is the MKL regime (the FMA chain at every
+ * n); the _chain one takes the chain from the caller (plain != 0: the naive loop).  The Python drop-in
+ * picks it from the per-batch shape; a homography without batch dimensions is `mm`, which is MKL at every
+ * n and the FMA chain from n = 11 points up. */
+
+/* transform_points_torch (utils.py:69-88): pts [M][n][3], homs [M][9] -> out [M][n][3] (the MKL regime) */
 int mpiv_transform_points(const float *pts, int M, int64_t n, const float *homs, float *out, void *stream);
+int mpiv_transform_points_chain(const float *pts, int M, int64_t n, const float *homs, int plain, float *out,
+                                void *stream);
 
 /* normalize_homogeneous_torch (utils.py:90-101): pts [n][k+1] -> out [n][k];
  * w == 0 is replaced by 1e-8 IN pts, as the reference's in-place `+=` does. */
 int mpiv_normalize_homogeneous(float *pts, int64_t n, int k, float *out, void *stream);
 
 /* pixel2cam_torch (utils.py:356-375): depth [B][n], pix [B][3][n], ki [B][9]
- * -> cam [B][3 or 4][n] */
+ * -> cam [B][3 or 4][n] (the MKL regime) */
 int mpiv_pixel2cam(const float *depth, const float *pix, const float *ki, int B, int64_t n, int homogeneous,
                    float *cam, void *stream);
+int mpiv_pixel2cam_chain(const float *depth, const float *pix, const float *ki, int B, int64_t n, int homogeneous,
+                         int plain, float *cam, void *stream);
 
-/* cam2pixel_torch (utils.py:377-393): cam [B][4][n], proj [B][16] -> out [B][n][2] */
+/* cam2pixel_torch (utils.py:377-393): cam [B][4][n], proj [B][16] -> out [B][n][2] (the MKL regime) */
 int mpiv_cam2pixel(const float *cam, const float *proj, int B, int64_t n, float *out, void *stream);
+int mpiv_cam2pixel_chain(const float *cam, const float *proj, int B, int64_t n, int plain, float *out, void *stream);
 
 /* transform_plane_imgs_torch coordinates (utils.py:176-188): pts [M][n][3],
- * homs [M][9] -> coords [M][n][2] = (u/w/(Ht-1), v/w/(Wt-1)) */
+ * homs [M][9] -> coords [M][n][2] = (u/w/(Ht-1), v/w/(Wt-1)) (the MKL regime) */
 int mpiv_plane_coords(const float *pts, int M, int64_t n, const float *homs, int Ht, int Wt, float *coords,
                       void *stream);
+int mpiv_plane_coords_chain(const float *pts, int M, int64_t n, const float *homs, int Ht, int Wt, int plain,
+                            float *coords, void *stream);
 
 /* ---- frame codec ------------------------------------------------------------ */
 

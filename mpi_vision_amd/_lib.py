@@ -133,7 +133,16 @@ _SIGS_HELPER_BWD = {
                                   _vp, _vp, ctypes.c_size_t, _vp],
     "mpiv_over_composite_backward": [_vp, _int, _i64, _i64, _i64, _vp, _c_i64p, _vp, _vp, ctypes.c_size_t, _vp],
 }
-EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_F16_TRAIN) + tuple(_SIGS_WARP) + tuple(_SIGS_PSV) + tuple(_SIGS_HELPER_BWD) + (
+# the matmul helpers with the chain as an argument (geometry.hip dot<>): on their own for the same reason.
+# They launch the kernels of the entries without `plain`, whose side-stream and graph-replay cases cover
+# them; tests/test_geometry_gpu.py runs both chains.
+_SIGS_CHAIN = {
+    "mpiv_transform_points_chain": [_vp, _int, _i64, _vp, _int, _vp, _vp],
+    "mpiv_pixel2cam_chain": [_vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp],
+    "mpiv_cam2pixel_chain": [_vp, _vp, _int, _i64, _int, _vp, _vp],
+    "mpiv_plane_coords_chain": [_vp, _int, _i64, _vp, _int, _int, _int, _vp, _vp],
+}
+EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_F16_TRAIN) + tuple(_SIGS_WARP) + tuple(_SIGS_PSV) + tuple(_SIGS_HELPER_BWD) + tuple(_SIGS_CHAIN) + (
                           "mpiv_grid_sample_backward_workspace_size", "mpiv_over_composite_backward_workspace_size",
                           "mpiv_plane_sweep_backward_workspace_size", "mpiv_plane_sweep_backward_workspace_size_min",
                           "mpiv_inverse_warp_backward_workspace_size","mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
@@ -199,7 +208,7 @@ def _open(path: str, check_id: bool):
     L.mpiv_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int]
     L.mpiv_debug_set.restype = ctypes.c_int
     for name, args in (*_SIGS.items(), *_SIGS_CAM.items(), *_SIGS_ALPHA.items(), *_SIGS_F16_TRAIN.items(),
-                       *_SIGS_WARP.items(), *_SIGS_PSV.items(), *_SIGS_HELPER_BWD.items()):
+                       *_SIGS_WARP.items(), *_SIGS_PSV.items(), *_SIGS_HELPER_BWD.items(), *_SIGS_CHAIN.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int
@@ -1899,6 +1908,13 @@ class OverCompositeFunction(torch.autograd.Function):
 # geometry helpers
 # ---------------------------------------------------------------------------
 
+def aten_plain(contraction: int, rows: int, cols: int) -> bool:
+    """How the reference's torch.matmul rounds a batched product on the CPU: ATen's bmm runs a naive loop
+    (plain products summed in ascending k) below 400 multiply-adds per batch element and hands larger
+    products to MKL sgemm (a chain of fused multiply-adds).  The kernels take the chain as an argument."""
+    return contraction * rows * cols < 400
+
+
 def transform_points(points: torch.Tensor, homography: torch.Tensor) -> torch.Tensor:
     dev = _dev(points, homography)
     hshape = list(homography.shape)
@@ -1908,7 +1924,9 @@ def transform_points(points: torch.Tensor, homography: torch.Tensor) -> torch.Te
     pts = points.reshape(hshape[:-2] + [-1, 3]).contiguous()
     n = pts.shape[-2]
     out = torch.empty_like(pts)
-    _call("mpiv_transform_points", pts, M, n, homography.reshape(M, 9).contiguous(), out,
+    # [M,n,3] @ [M,3,3]^T; a homography without batch dimensions is `mm`: MKL at every n
+    plain = len(hshape) > 2 and aten_plain(3, n, 3)
+    _call("mpiv_transform_points_chain", pts, M, n, homography.reshape(M, 9).contiguous(), int(plain), out,
           _stream(dev))
     return out.reshape(points.shape)
 
@@ -1934,8 +1952,9 @@ def pixel2cam(depth, pixel_coords, intrinsics, is_homogeneous=True):
     ki = torch.inverse(_cpu32(intrinsics)).reshape(B, 9)
     rows = 4 if is_homogeneous else 3
     cam = torch.empty((B, rows, H, W), device=dev, dtype=torch.float32)
-    _call("mpiv_pixel2cam", depth.contiguous(), pixel_coords.reshape(B, 3, n).contiguous(),
-          _up(ki, dev, "inverse(intrinsics)"), B, n, int(bool(is_homogeneous)), cam, _stream(dev))
+    _call("mpiv_pixel2cam_chain", depth.contiguous(), pixel_coords.reshape(B, 3, n).contiguous(),
+          _up(ki, dev, "inverse(intrinsics)"), B, n, int(bool(is_homogeneous)), int(aten_plain(3, 3, n)), cam,
+          _stream(dev))  # [B,3,3] @ [B,3,n]
     return cam
 
 
@@ -1944,8 +1963,8 @@ def cam2pixel(cam_coords, proj):
     B, _, H, W = cam_coords.shape
     n = H * W
     out = torch.empty((B, H, W, 2), device=dev, dtype=torch.float32)
-    _call("mpiv_cam2pixel", cam_coords.reshape(B, 4, n).contiguous(), proj.reshape(B, 16).contiguous(), B,
-          n, out, _stream(dev))
+    _call("mpiv_cam2pixel_chain", cam_coords.reshape(B, 4, n).contiguous(), proj.reshape(B, 16).contiguous(), B,
+          n, int(aten_plain(4, 4, n)), out, _stream(dev))  # [B,4,4] @ [B,4,n]
     return out
 
 
@@ -1960,6 +1979,7 @@ def warp_planes(imgs: torch.Tensor, pixel_coords_trg: torch.Tensor, hom: torch.T
     Ht, Wt = pixel_coords_trg.shape[-3], pixel_coords_trg.shape[-2]
     pts = pixel_coords_trg.reshape(M, Ht * Wt, 3).contiguous()
     coords = torch.empty((M, Ht, Wt, 2), device=dev, dtype=torch.float32)
-    _call("mpiv_plane_coords", pts, M, Ht * Wt, _up(hom.reshape(M, 9), dev, "hom"), Ht, Wt, coords,
-          _stream(dev))
+    plain = len(hshape) > 2 and aten_plain(3, Ht * Wt, 3)  # transform_points_torch's product
+    _call("mpiv_plane_coords_chain", pts, M, Ht * Wt, _up(hom.reshape(M, 9), dev, "hom"), Ht, Wt, int(plain),
+          coords, _stream(dev))
     return bilinear_sample(imgs, coords.reshape(list(pixel_coords_trg.shape[:-1]) + [2]), channels_last_out=False)

@@ -2212,11 +2212,22 @@ int mpiv_over_composite_backward(const float* const* layers, int P, int64_t n, i
     return launched(nm);
 }
 
-int mpiv_transform_points(const float* pts, int M, int64_t n, const float* homs, float* out, void* stream) {
+// The four matmul helpers: the entry without a `plain` argument is the MKL regime (the FMA chain at every
+// size, as before); the _chain entry takes the chain from the caller (geometry.hip dot<>).
+int mpiv_transform_points_chain(const float* pts, int M, int64_t n, const float* homs, int plain, float* out,
+                                void* stream) {
     if (!pts || !homs || !out) return fail(MPIV_ERR_ARG, "mpiv_transform_points: null pointer");
     if (M <= 0 || n <= 0 || M > kMaxGridYZ) return fail(MPIV_ERR_ARG, "mpiv_transform_points: bad shape");
-    transform_points_kernel<<<dim3(blocks(n, 256), M), 256, 0, S(stream)>>>(pts, n, homs, out);
+    const dim3 grid(blocks(n, 256), M);
+    if (plain)
+        transform_points_kernel<true><<<grid, 256, 0, S(stream)>>>(pts, n, homs, out);
+    else
+        transform_points_kernel<false><<<grid, 256, 0, S(stream)>>>(pts, n, homs, out);
     return launched("mpiv_transform_points");
+}
+
+int mpiv_transform_points(const float* pts, int M, int64_t n, const float* homs, float* out, void* stream) {
+    return mpiv_transform_points_chain(pts, M, n, homs, 0, out, stream);
 }
 
 int mpiv_normalize_homogeneous(float* pts, int64_t n, int k, float* out, void* stream) {
@@ -2226,29 +2237,55 @@ int mpiv_normalize_homogeneous(float* pts, int64_t n, int k, float* out, void* s
     return launched("mpiv_normalize_homogeneous");
 }
 
-int mpiv_pixel2cam(const float* depth, const float* pix, const float* ki, int B, int64_t n, int homogeneous,
-                   float* cam, void* stream) {
+int mpiv_pixel2cam_chain(const float* depth, const float* pix, const float* ki, int B, int64_t n, int homogeneous,
+                         int plain, float* cam, void* stream) {
     if (!depth || !pix || !ki || !cam) return fail(MPIV_ERR_ARG, "mpiv_pixel2cam: null pointer");
     if (B <= 0 || n <= 0 || B > kMaxGridYZ) return fail(MPIV_ERR_ARG, "mpiv_pixel2cam: bad shape");
-    pixel2cam_kernel<<<dim3(blocks(n, 256), B), 256, 0, S(stream)>>>(depth, pix, ki, n, homogeneous, cam);
+    const dim3 grid(blocks(n, 256), B);
+    if (plain)
+        pixel2cam_kernel<true><<<grid, 256, 0, S(stream)>>>(depth, pix, ki, n, homogeneous, cam);
+    else
+        pixel2cam_kernel<false><<<grid, 256, 0, S(stream)>>>(depth, pix, ki, n, homogeneous, cam);
     return launched("mpiv_pixel2cam");
 }
 
-int mpiv_cam2pixel(const float* cam, const float* proj, int B, int64_t n, float* out, void* stream) {
+int mpiv_pixel2cam(const float* depth, const float* pix, const float* ki, int B, int64_t n, int homogeneous,
+                   float* cam, void* stream) {
+    return mpiv_pixel2cam_chain(depth, pix, ki, B, n, homogeneous, 0, cam, stream);
+}
+
+int mpiv_cam2pixel_chain(const float* cam, const float* proj, int B, int64_t n, int plain, float* out, void* stream) {
     if (!cam || !proj || !out) return fail(MPIV_ERR_ARG, "mpiv_cam2pixel: null pointer");
     if (B <= 0 || n <= 0 || B > kMaxGridYZ) return fail(MPIV_ERR_ARG, "mpiv_cam2pixel: bad shape");
-    cam2pixel_kernel<<<dim3(blocks(n, 256), B), 256, 0, S(stream)>>>(cam, proj, n, out);
+    const dim3 grid(blocks(n, 256), B);
+    if (plain)
+        cam2pixel_kernel<true><<<grid, 256, 0, S(stream)>>>(cam, proj, n, out);
+    else
+        cam2pixel_kernel<false><<<grid, 256, 0, S(stream)>>>(cam, proj, n, out);
     return launched("mpiv_cam2pixel");
+}
+
+int mpiv_cam2pixel(const float* cam, const float* proj, int B, int64_t n, float* out, void* stream) {
+    return mpiv_cam2pixel_chain(cam, proj, B, n, 0, out, stream);
+}
+
+int mpiv_plane_coords_chain(const float* pts, int M, int64_t n, const float* homs, int Ht, int Wt, int plain,
+                            float* coords, void* stream) {
+    if (!pts || !homs || !coords) return fail(MPIV_ERR_ARG, "mpiv_plane_coords: null pointer");
+    if (M <= 0 || n <= 0 || M > kMaxGridYZ || Ht <= 0 || Wt <= 0)
+        return fail(MPIV_ERR_ARG, "mpiv_plane_coords: bad shape");
+    const dim3 grid(blocks(n, 256), M);
+    const float hm1 = (float)(Ht - 1), wm1 = (float)(Wt - 1);
+    if (plain)
+        plane_coords_kernel<true><<<grid, 256, 0, S(stream)>>>(pts, n, homs, hm1, wm1, coords);
+    else
+        plane_coords_kernel<false><<<grid, 256, 0, S(stream)>>>(pts, n, homs, hm1, wm1, coords);
+    return launched("mpiv_plane_coords");
 }
 
 int mpiv_plane_coords(const float* pts, int M, int64_t n, const float* homs, int Ht, int Wt, float* coords,
                       void* stream) {
-    if (!pts || !homs || !coords) return fail(MPIV_ERR_ARG, "mpiv_plane_coords: null pointer");
-    if (M <= 0 || n <= 0 || M > kMaxGridYZ || Ht <= 0 || Wt <= 0)
-        return fail(MPIV_ERR_ARG, "mpiv_plane_coords: bad shape");
-    plane_coords_kernel<<<dim3(blocks(n, 256), M), 256, 0, S(stream)>>>(pts, n, homs, (float)(Ht - 1),
-                                                                        (float)(Wt - 1), coords);
-    return launched("mpiv_plane_coords");
+    return mpiv_plane_coords_chain(pts, M, n, homs, Ht, Wt, 0, coords, stream);
 }
 
 int mpiv_preprocess(const float* in, int64_t n, float* out, void* stream) {

@@ -42,6 +42,14 @@ def test_abi_version():
     ("mpiv_grid_sample", [None, None, 1, 1, 4, 4, None, None, 2, 2, None, None, None]),
     ("mpiv_over_composite", [None, 2, 4, 4, 1, None, None]),
     ("mpiv_combine_ct", [None, 2, 4, None, None]),
+    ("mpiv_transform_points", [None, 2, 4, None, None, None]),
+    ("mpiv_transform_points_chain", [None, 2, 4, None, 1, None, None]),
+    ("mpiv_pixel2cam", [None, None, None, 2, 4, 1, None, None]),
+    ("mpiv_pixel2cam_chain", [None, None, None, 2, 4, 1, 1, None, None]),
+    ("mpiv_cam2pixel", [None, None, 2, 4, None, None]),
+    ("mpiv_cam2pixel_chain", [None, None, 2, 4, 1, None, None]),
+    ("mpiv_plane_coords", [None, 2, 4, None, 3, 3, None, None]),
+    ("mpiv_plane_coords_chain", [None, 2, 4, None, 3, 3, 1, None, None]),
 ])
 def test_null_pointers_rejected(call):
     name, args = call
@@ -49,6 +57,25 @@ def test_null_pointers_rejected(call):
     rc = getattr(L, name)(*args)
     assert rc == -1
     assert b"null pointer" in L.mpiv_last_error()
+
+
+def test_chain_entries_are_bound_beside_the_old_ones():
+    """The matmul helpers' additive _chain entries (an explicit `plain` argument after the old entry's
+    inputs): declared, exported, bound on their own table, and the ABI version stays."""
+    L = _lib.load_main()
+    for old in ("mpiv_transform_points", "mpiv_pixel2cam", "mpiv_cam2pixel", "mpiv_plane_coords"):
+        new = old + "_chain"
+        assert new in declared_symbols() and new in _lib.EXPORTS and new in _lib._SIGS_CHAIN and new not in _lib._SIGS
+        assert getattr(L, new).argtypes == _lib._SIGS_CHAIN[new]
+        sig = list(_lib._SIGS_CHAIN[new])
+        assert len(sig) == len(_lib._SIGS[old]) + 1 and sig[-3] is ctypes.c_int  # ..., plain, out, stream
+        assert sig[:-3] + sig[-2:] == _lib._SIGS[old]
+        p = ctypes.c_void_p(256)
+        args = [p if t is ctypes.c_void_p else 0 for t in sig]  # every size 0: refused before any launch
+        assert getattr(L, new)(*args) == -1 and b"bad shape" in L.mpiv_last_error()
+    assert L.mpiv_abi_version() == 17 == _lib.ABI_VERSION
+    assert _lib.aten_plain(3, 44, 3) and not _lib.aten_plain(3, 45, 3)
+    assert _lib.aten_plain(4, 4, 24) and not _lib.aten_plain(4, 4, 25)
 
 
 def test_bad_shapes_rejected():

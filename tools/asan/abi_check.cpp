@@ -54,6 +54,10 @@ int main() {
     EXPECT(mpiv_pixel2cam(f, f, f, 1, 0, 1, f, nullptr) == MPIV_ERR_ARG);
     EXPECT(mpiv_cam2pixel(nullptr, f, 1, 4, f, nullptr) == MPIV_ERR_ARG);
     EXPECT(mpiv_plane_coords(f, 1, 4, f, 0, 4, f, nullptr) == MPIV_ERR_ARG);
+    EXPECT(mpiv_transform_points_chain(f, 0, 4, f, 1, f, nullptr) == MPIV_ERR_ARG);
+    EXPECT(mpiv_pixel2cam_chain(f, f, f, 1, 0, 1, 1, f, nullptr) == MPIV_ERR_ARG);
+    EXPECT(mpiv_cam2pixel_chain(nullptr, f, 1, 4, 1, f, nullptr) == MPIV_ERR_ARG);
+    EXPECT(mpiv_plane_coords_chain(f, 1, 4, f, 0, 4, 1, f, nullptr) == MPIV_ERR_ARG);
     EXPECT(mpiv_preprocess(f, 0, f, nullptr) == MPIV_ERR_ARG);
     EXPECT(mpiv_deprocess_u8(f, 0, nullptr, nullptr) == MPIV_ERR_ARG);
     EXPECT(mpiv_assemble_mpi(f, st4, f, st4, 1, 4, 4, 0, f, nullptr) == MPIV_ERR_ARG);
