@@ -111,6 +111,11 @@ __device__ __forceinline__ void render_pos_fast(const float* __restrict__ h, flo
 // -- the refined reciprocal of w, qu, px, floor(px), the x weights and the clamped tap column -- is
 // then computed once per (lane, plane) at the lane's first row, with the same expressions (the same
 // bits), and the rows run only the v chain: ~23 of a continuing row's ~87 VALU.
+//
+// The rows of a separable view form the tap address as __mul24(cy, row pitch in bytes) + coff (one
+// v_mad_i32_i24), exact while the pitch fits 24 signed bits; wider rows keep the row recipe.
+constexpr int kColsepMaxPitch = 1 << 23;
+
 struct ColSet {
     float w, y;    // w and its refined reciprocal (div2_fast)
     float wx, ex;  // issue_taps_padded's x weights
@@ -549,7 +554,9 @@ __device__ __forceinline__ void render_rows_vs_pixels(const float4* __restrict__
         t.se = wy * wx;
         const int cy = (int)__builtin_amdgcn_fmed3f(fy0, -2.0f, (float)g.H);
         if constexpr (CS)
-            off = __mul24(cy, g.Wp) * 16 + col.coff;  // the same integer: (cy*Wp + cx)*16 + org
+            // the same integer as (cy*Wp + cx)*16 + org, in one 24-bit multiply-add: the kernel takes
+            // this path only while the byte pitch fits 24 bits (kColsepMaxPitch)
+            off = __mul24(cy, g.row) + col.coff;
         else
             off = (__mul24(cy, g.Wp) + off) * 16 + g.org;
         t.off = off;
@@ -617,6 +624,8 @@ __device__ __forceinline__ void render_rows_vs_pixels(const float4* __restrict__
             acc = __builtin_fmaf(sd_[c], t.se, acc);
             s[c] = acc;
         }
+        // (the select stays here: on a stretched MPI most rows have a lane that stayed, so consume's two
+        // arms would put the common rows in the arm with the selects -- measured slower)
         const float a = first ? 1.0f : s[3];
         const float om = 1.0f - a;
         cr[k] = over(s[0], a, om, cr[k]);
@@ -628,31 +637,44 @@ __device__ __forceinline__ void render_rows_vs_pixels(const float4* __restrict__
         pa = na; pb = nb; pc = sc_; pd = sd_;
     };
     auto consume = [&](const RowTaps& t, const f32x4& pc, const f32x4& pd, int k, bool first) {
+        auto blend = [&](const f32x4& na, const f32x4& nb) {  // blend_taps' fma chain
+            f32x4 s;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float acc = na[c] * t.nw;
+                acc = __builtin_fmaf(nb[c], t.ne, acc);
+                acc = __builtin_fmaf(t.c[c], t.sw, acc);
+                acc = __builtin_fmaf(t.d[c], t.se, acc);
+                s[c] = acc;
+            }
+            return s;
+        };
         f32x4 s;
-        f32x4 na = pc, nb = pd;  // every lane continues (the common case): no per-lane select
+        float a;
 #ifndef MPIV_VS_BRANCH
 #define MPIV_VS_BRANCH 1
 #endif
-        if (!MPIV_VS_BRANCH || t.own) {
+        // Two arms of one wave-uniform branch, each with its own blend.  The rare arm: some lane
+        // gathered its own north taps (per-lane selects), or the plane is p_begin, whose alpha is
+        // replaced by 1 (one plane in P).  The common arm -- every lane continues on a later plane --
+        // has neither the tap selects nor the alpha select.
+        if (!MPIV_VS_BRANCH || t.own || first) {
 #ifndef MPIV_VS_ASMBR
 #define MPIV_VS_ASMBR 1
 #endif
-            if (MPIV_VS_ASMBR) asm volatile("");  // keeps this a real (wave-uniform) branch: if-converted, its 8 selects ran always
+            if (MPIV_VS_ASMBR) asm volatile("");  // keeps this a real (wave-uniform) branch: if-converted, its selects ran always
+            f32x4 na, nb;
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 na[c] = t.sh ? pc[c] : t.a[c];
                 nb[c] = t.sh ? pd[c] : t.b[c];
             }
+            s = blend(na, nb);
+            a = first ? 1.0f : s[3];
+        } else {
+            s = blend(pc, pd);
+            a = s[3];
         }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {  // blend_taps' fma chain
-            float acc = na[c] * t.nw;
-            acc = __builtin_fmaf(nb[c], t.ne, acc);
-            acc = __builtin_fmaf(t.c[c], t.sw, acc);
-            acc = __builtin_fmaf(t.d[c], t.se, acc);
-            s[c] = acc;
-        }
-        const float a = first ? 1.0f : s[3];
         const float om = 1.0f - a;
         cr[k] = over(s[0], a, om, cr[k]);
         cg[k] = over(s[1], a, om, cg[k]);
@@ -865,12 +887,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SAME && R =
     const bool proven = __syncthreads_and(ok);
     const bool dead = __syncthreads_and(dd);
     // column-separable view (ColSet): every plane of the range has h[1] == h[7] == 0.  colsep (the
-    // render_colsep option): 0 automatic, -1 never, 1 without the test (a test hook)
+    // render_colsep option): 0 automatic, -1 never, 1 without the test (a test hook); never where the
+    // row pitch does not fit the path's 24-bit tap address (kColsepMaxPitch), the option at 1 included
     // (the (C, T) same-row flavour with R = 8, reached through debug options only, keeps the row
     // recipe: with both row loops it spills two SGPRs)
     constexpr bool COLSEP = VS && !(CT && SAME && R == 8);
     bool sep = false;
-    if constexpr (COLSEP) sep = colsep > 0 || (colsep == 0 && __syncthreads_and(cs));
+    if constexpr (COLSEP)
+        sep = g.row < kColsepMaxPitch && (colsep > 0 || (colsep == 0 && __syncthreads_and(cs)));
     if (x >= g.W || y0 >= y_hi) return;  // rows past y_hi inside [y0, y0+R) are computed, not stored
     float cr[R], cg[R], cb[R], tt[R];
 #pragma unroll

@@ -347,7 +347,7 @@ __device__ __forceinline__ void render_tex_vs_pixels(const typename T::Texel* __
         t.wy = py - fy0;
         const int cy = (int)__builtin_amdgcn_fmed3f(fy0, -2.0f, (float)g.H);
         if constexpr (CS)
-            off = __mul24(cy, g.Wp) * T::kBytes + col.coff;  // the same integer: (cy*Wp + cx)*kBytes + org
+            off = __mul24(cy, tg.row) + col.coff;  // (cy*Wp + cx)*kBytes + org; tg.row < kColsepMaxPitch (render.hip)
         else
             off = (__mul24(cy, g.Wp) + off) * T::kBytes + tg.org;
         t.off = off;
@@ -502,9 +502,10 @@ __device__ __forceinline__ void render_tex_tile(const typename T::Texel* __restr
     }
     const bool proven = __syncthreads_and(ok);
     const bool dead = __syncthreads_and(dd);
-    // column-separable view (render.hip ColSet; colsep as render_rows_kernel's)
+    // column-separable view (render.hip ColSet; colsep and the pitch bound as render_rows_kernel's)
     bool sep = false;
-    if constexpr (VS) sep = colsep > 0 || (colsep == 0 && __syncthreads_and(cs));
+    if constexpr (VS)
+        sep = tg.row < kColsepMaxPitch && (colsep > 0 || (colsep == 0 && __syncthreads_and(cs)));
     if (x >= g.W || y0 >= g.H) return;  // rows past H inside [y0, y0+R) are computed, not stored
     float cr[R], cg[R], cb[R], tt[R];
 #pragma unroll
