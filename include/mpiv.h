@@ -79,6 +79,10 @@ int mpiv_debug_set(const char *name, int value);
  *   "render_packed_u8"                   {H, W, P, V}        (mpiv_render_packed_u8)
  *   "render_packed_f16", "render_packed_f16_ct"  {H, W, P, V} (mpiv_render_packed_f16[_ct])
  *   "render_packed_alpha"                {H, W, P, V}        (mpiv_render_packed_alpha)
+ *   "render_packed_tgt", "render_packed_u8_tgt", "render_packed_f16_tgt"
+ *                                        {Hs, Ws, P, V, Ht, Wt} (mpiv_render_packed[_u8|_f16]_tgt: the
+ *                                                            render_*_tgt_kernel twins; with Ht == Hs and
+ *                                                            Wt == Ws the same-size kernel itself)
  *   "render_net_output"                  {B, H, W, P}        (mpiv_render_net_output)
  *   "render_train"                       {B, H, W, P}        (mpiv_render_train, contiguous MPI)
  *   "render_backward"                    {B, H, W, P}        (mpiv_render_backward, contiguous MPI, the
@@ -129,6 +133,18 @@ int mpiv_pack_planes(const float *mpi_view, const int64_t strides[4], int H, int
  * the views of one output tile share an XCD's L2 (render.hip). */
 int mpiv_render_packed(const float *packed, int H, int W, int P, const float *homs, int V,
                        float *out, void *stream);
+
+/* mpiv_render_packed into a target frame of its own size: the packed MPI is Hs x Ws, the frame
+ * out [V,Ht,Wt,3].  Target pixel (x, y) of the Ht x Wt grid goes through the plane's homography
+ * (built with K = the source intrinsics and Kinv = the inverse of the target's,
+ * mpiv_render_homographies) and the source pixel coordinate it lands on is normalised as the
+ * reference's planar_transform_torch does it, x_s / (Ht - 1) and y_s / (Wt - 1) (swapped, from
+ * pixel_coords_trg), then unnormalised by grid_sample over the Ws x Hs source: the sample is at
+ * x_s * Ws / (Ht - 1) - 0.5, y_s * Hs / (Wt - 1) - 0.5.  Same recipe, blend and composite as
+ * mpiv_render_packed; with Ht == Hs and Wt == Ws it is that launch.  The source's padded plane
+ * must stay below 2 GiB; a dimension below 2 on either side takes the generic recipe. */
+int mpiv_render_packed_tgt(const float *packed, int Hs, int Ws, int P, const float *homs, int V,
+                           int Ht, int Wt, float *out, void *stream);
 
 /* mpiv_render_packed through the counting build of render_rows_kernel (same frames): adds to
  * *census (device, caller-zeroed) the number of 64-lane 16-B gather instructions the launch
@@ -569,6 +585,10 @@ int mpiv_pack_planes_u8(const uint8_t *mpi_view, const int64_t strides[4], int H
 int mpiv_render_packed_u8(const uint32_t *packed, int H, int W, int P, const float *homs, int V, float *out,
                           void *stream);
 
+/* mpiv_render_packed_tgt on a packed u8 MPI (out [V,Ht,Wt,3]; all four dimensions >= 2). */
+int mpiv_render_packed_u8_tgt(const uint32_t *packed, int Hs, int Ws, int P, const float *homs, int V,
+                              int Ht, int Wt, float *out, void *stream);
+
 /* mpiv_render_packed_ct on a packed u8 MPI (plane-range partial (C, T) [V,H,W,4]). */
 int mpiv_render_packed_u8_ct(const uint32_t *packed, int H, int W, int P, int p_begin, int p_end, int back,
                              const float *homs, int V, float *ct, void *stream);
@@ -604,6 +624,10 @@ int mpiv_unpack_planes_f16(const uint16_t *packed, int H, int W, int P, float *o
  * reference's blend).  H, W >= 2. */
 int mpiv_render_packed_f16(const uint16_t *packed, int H, int W, int P, const float *homs, int V,
                            float *out, void *stream);
+
+/* mpiv_render_packed_tgt on a packed f16 MPI (out [V,Ht,Wt,3]; all four dimensions >= 2). */
+int mpiv_render_packed_f16_tgt(const uint16_t *packed, int Hs, int Ws, int P, const float *homs, int V,
+                               int Ht, int Wt, float *out, void *stream);
 
 /* mpiv_render_packed_ct on a packed f16 MPI (plane-range partial (C, T) [V,H,W,4], 16-B aligned). */
 int mpiv_render_packed_f16_ct(const uint16_t *packed, int H, int W, int P, int p_begin, int p_end,

@@ -179,20 +179,29 @@ def captured_constant(host: torch.Tensor, dev) -> torch.Tensor:
 
 
 def render_homographies_device(pose: torch.Tensor, depths: torch.Tensor, intrinsics: torch.Tensor,
-                               batch: int) -> torch.Tensor:
+                               batch: int, tgt_intrinsics: torch.Tensor | None = None) -> torch.Tensor:
     """render_homographies for a pose batch that lives on a ROCm device: the same chain
     evaluated there (mpiv_render_homographies_device, bit-identical to the host entry),
     so the render path issues no blocking device-to-host copy of the poses.  Returns a
-    [B, P, 9] fp32 tensor on the pose's device."""
+    [B, P, 9] fp32 tensor on the pose's device.
+    tgt_intrinsics (mpi_render_view_torch2): k_s = intrinsics, k_t = tgt_intrinsics, whose inverse
+    is the memoised one (_kinv_device); k_s is read from the caller's own tensor."""
     from . import _lib
     dev = pose.device
+    if tgt_intrinsics is not None and intrinsics.device != dev:
+        # k_s is read live (no memo pairs it with an inverse): its upload cannot be part of a captured graph
+        _lib.host_under_capture("src_intrinsics")
     pose_d = _f32_on(pose, dev).contiguous()
     d = _f32_on(depths, dev).reshape(-1).contiguous()
     K = _f32_on(intrinsics, dev)
     if tuple(K.shape) != (batch, 3, 3):
         K = K.expand(batch, 3, 3)
     K = K.contiguous()
-    kinv, k_const = _kinv_device(intrinsics, batch, dev, with_k=True)
+    if tgt_intrinsics is not None:
+        kinv = _kinv_device(tgt_intrinsics, batch, dev)
+        k_const = None
+    else:
+        kinv, k_const = _kinv_device(intrinsics, batch, dev, with_k=True)
     if k_const is not None:  # under a HIP-graph capture: the K its inverse was taken from
         K = k_const
     P = d.shape[0]
@@ -202,7 +211,7 @@ def render_homographies_device(pose: torch.Tensor, depths: torch.Tensor, intrins
 
 
 def render_homographies(pose: torch.Tensor, depths: torch.Tensor, intrinsics: torch.Tensor,
-                        batch: int, pin: bool = False) -> torch.Tensor:
+                        batch: int, pin: bool = False, tgt_intrinsics: torch.Tensor | None = None) -> torch.Tensor:
     """Per-(view, plane) target->source homographies for mpi_render_view_torch
     (utils.py:278-285 -> 255-262 -> 225-229 -> 44-67), as a [B, P, 9] fp32 CPU tensor
     (page-locked with pin=True, ready for an asynchronous upload).
@@ -211,13 +220,16 @@ def render_homographies(pose: torch.Tensor, depths: torch.Tensor, intrinsics: to
     of these tiny matrices is plain products summed in ascending k, which the library
     restates exactly; only K^-1 comes from torch.inverse (LAPACK), as in the reference.
     ~35 tiny torch ops (~0.2 ms of dispatch) become one call.  render_homographies_torch
-    keeps the op-by-op form (tests compare the two bit for bit)."""
+    keeps the op-by-op form (tests compare the two bit for bit).
+    tgt_intrinsics (mpi_render_view_torch2; planar_transform_torch's separate k_s and k_t):
+    K = intrinsics (k_s) and K^-1 = inverse(tgt_intrinsics), from the same memoised torch.inverse
+    of its contiguous [B,3,3] batch."""
     from . import _lib
     pose = _cpu32(pose).contiguous()
     K = _cpu32(intrinsics).expand(batch, 3, 3).contiguous()
     d = _cpu32(depths).reshape(-1).contiguous()
     P = d.shape[0]
-    kinv = _inverse_cached(K)
+    kinv = _inverse_cached(K if tgt_intrinsics is None else _cpu32(tgt_intrinsics).expand(batch, 3, 3).contiguous())
     H = torch.empty((batch, P, 9), dtype=_F32, pin_memory=pin)
     rc = _lib.load().mpiv_render_homographies(pose.data_ptr(), d.data_ptr(), K.data_ptr(), kinv.data_ptr(),
                                               batch, P, H.data_ptr())

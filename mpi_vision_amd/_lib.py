@@ -142,7 +142,14 @@ _SIGS_CHAIN = {
     "mpiv_cam2pixel_chain": [_vp, _vp, _int, _i64, _int, _vp, _vp],
     "mpiv_plane_coords_chain": [_vp, _int, _i64, _vp, _int, _int, _int, _vp, _vp],
 }
-EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_F16_TRAIN) + tuple(_SIGS_WARP) + tuple(_SIGS_PSV) + tuple(_SIGS_HELPER_BWD) + tuple(_SIGS_CHAIN) + (
+# the packed renders into a target frame of its own size (render.hip RenderGeomT): on their own for the same
+# reason; their side-stream and graph-replay cases are in tests/test_target_gpu.py.
+_SIGS_TGT = {
+    "mpiv_render_packed_tgt": [_vp, _int, _int, _int, _vp, _int, _int, _int, _vp, _vp],
+    "mpiv_render_packed_u8_tgt": [_vp, _int, _int, _int, _vp, _int, _int, _int, _vp, _vp],
+    "mpiv_render_packed_f16_tgt": [_vp, _int, _int, _int, _vp, _int, _int, _int, _vp, _vp],
+}
+EXPORTS = tuple(_SIGS) + tuple(_SIGS_CAM) + tuple(_SIGS_ALPHA) + tuple(_SIGS_TGT) + tuple(_SIGS_F16_TRAIN) + tuple(_SIGS_WARP) + tuple(_SIGS_PSV) + tuple(_SIGS_HELPER_BWD) + tuple(_SIGS_CHAIN) + (
                           "mpiv_grid_sample_backward_workspace_size", "mpiv_over_composite_backward_workspace_size",
                           "mpiv_plane_sweep_backward_workspace_size", "mpiv_plane_sweep_backward_workspace_size_min",
                           "mpiv_inverse_warp_backward_workspace_size","mpiv_abi_version", "mpiv_last_error", "mpiv_render_backward_workspace_size",
@@ -208,7 +215,8 @@ def _open(path: str, check_id: bool):
     L.mpiv_debug_set.argtypes = [ctypes.c_char_p, ctypes.c_int]
     L.mpiv_debug_set.restype = ctypes.c_int
     for name, args in (*_SIGS.items(), *_SIGS_CAM.items(), *_SIGS_ALPHA.items(), *_SIGS_F16_TRAIN.items(),
-                       *_SIGS_WARP.items(), *_SIGS_PSV.items(), *_SIGS_HELPER_BWD.items(), *_SIGS_CHAIN.items()):
+                       *_SIGS_WARP.items(), *_SIGS_PSV.items(), *_SIGS_HELPER_BWD.items(), *_SIGS_CHAIN.items(),
+                       *_SIGS_TGT.items()):
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = ctypes.c_int
@@ -567,20 +575,36 @@ def _tex_unpack(t: _Tex, packed: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def _render_views(what: str, packed: torch.Tensor, phw, homs: torch.Tensor, out: torch.Tensor | None):
-    """mpiv_<what>: a packed MPI of any format + homs [V,P,9] (host or device) -> [V,H,W,3]."""
+def _render_views(what: str, packed: torch.Tensor, phw, homs: torch.Tensor, out: torch.Tensor | None, size=None):
+    """mpiv_<what>: a packed MPI of any format + homs [V,P,9] (host or device) -> [V,H,W,3]; with
+    size = (Ht, Wt), mpiv_<what>_tgt: a target frame of its own size [V,Ht,Wt,3]."""
     P, H, W = phw
     dev = packed.device
     V = homs.shape[0]
     h = _up(homs.reshape(V, P, 9), dev, "homs")
+    Ht, Wt = (H, W) if size is None else _target_size(size)
     if out is None:
-        out = torch.empty((V, H, W, 3), device=dev, dtype=torch.float32)
+        out = torch.empty((V, Ht, Wt, 3), device=dev, dtype=torch.float32)
     else:
-        _check_out(out, (V, H, W, 3), dev, what)
+        _check_out(out, (V, Ht, Wt, 3), dev, what)
     if V == 0:
         return out
-    _call(f"mpiv_{what}", packed, H, W, P, h, V, out, _stream(dev))
+    if size is None:
+        _call(f"mpiv_{what}", packed, H, W, P, h, V, out, _stream(dev))
+    else:
+        _call(f"mpiv_{what}_tgt", packed, H, W, P, h, V, Ht, Wt, out, _stream(dev))
     return out
+
+
+def _target_size(size):
+    """(Ht, Wt) of a render's size= argument: two positive ints."""
+    try:
+        Ht, Wt = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"size must be (target height, target width), got {size!r}") from None
+    if Ht <= 0 or Wt <= 0:
+        raise RuntimeError(f"size must be (target height, target width) > 0, got {size!r}")
+    return Ht, Wt
 
 
 def _render_views_ct(what: str, packed: torch.Tensor, phw, homs: torch.Tensor, back: bool, p_begin: int,
@@ -600,15 +624,15 @@ def _render_views_ct(what: str, packed: torch.Tensor, phw, homs: torch.Tensor, b
 
 
 def _tex_render(t: _Tex, packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None,
-                route_float: bool | None) -> torch.Tensor:
+                route_float: bool | None, size=None) -> torch.Tensor:
     phw = _tex_hw(t, packed)
     if route_float is None:
         route_float = homs.shape[0] >= t.float_min_views
     if route_float:
         if homs.device.type == "cpu":
             host_under_capture("homs")  # (before the float copy is launched)
-        return render_packed(packed_float_copy(packed), homs, out=out)
-    return _render_views(f"render_packed_{t.name}", packed, phw, homs, out)
+        return render_packed(packed_float_copy(packed), homs, out=out, size=size)
+    return _render_views(f"render_packed_{t.name}", packed, phw, homs, out, size)
 
 
 def pack_planes_u8(view: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -716,12 +740,13 @@ clear_u8_float_copies = clear_float_copies
 
 
 def render_packed_u8(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None = None,
-                     route_float: bool | None = None) -> torch.Tensor:
+                     route_float: bool | None = None, size=None) -> torch.Tensor:
     """packed u8 [P,H+4,W+4] + homs [V,P,9] -> [V,H,W,3] fp32, bit-identical to rendering the
     float MPI u8.float() / 255 (render_texel.hip).  Launches of >= U8_FLOAT_MIN_VIEWS views
     (route_float None) render the MPI's exact float copy (u8_float_copy, converted once per MPI)
-    with the float kernel instead: the same bits, faster where the texture path binds."""
-    return _tex_render(_U8, packed, homs, out, route_float)
+    with the float kernel instead: the same bits, faster where the texture path binds.
+    size = (Ht, Wt): a target frame of its own size [V,Ht,Wt,3] (render_packed)."""
+    return _tex_render(_U8, packed, homs, out, route_float, size)
 
 
 def render_packed_u8_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_begin: int = 0,
@@ -731,13 +756,14 @@ def render_packed_u8_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_
 
 
 def render_packed_f16(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None = None,
-                      route_float: bool | None = None) -> torch.Tensor:
+                      route_float: bool | None = None, size=None) -> torch.Tensor:
     """packed f16 [P,H+4,W+4,4] + homs [V,P,9] -> [V,H,W,3] fp32, bit-identical to rendering the
     float MPI mpi.float() (render_texel.hip: half the texel bytes of the float render).  Launches of
     >= F16_FLOAT_MIN_VIEWS views (route_float None) render the MPI's exact float copy
     (f16_float_copy, converted once per MPI) with the float kernel instead: the same bits, faster
-    where the texture path binds (it costs the float copy's memory, 2x the f16 MPI)."""
-    return _tex_render(_F16, packed, homs, out, route_float)
+    where the texture path binds (it costs the float copy's memory, 2x the f16 MPI).
+    size = (Ht, Wt): a target frame of its own size [V,Ht,Wt,3] (render_packed)."""
+    return _tex_render(_F16, packed, homs, out, route_float, size)
 
 
 def render_packed_f16_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_begin: int = 0,
@@ -805,10 +831,15 @@ def unpack_planes(packed: torch.Tensor) -> torch.Tensor:
     return packed[:, PAD:PAD + H, PAD:PAD + W].permute(1, 2, 0, 3)
 
 
-def render_packed(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-    """packed [P,H+4,W+4,4] + homs [V,P,9] (host or device) -> [V,H,W,3]."""
+def render_packed(packed: torch.Tensor, homs: torch.Tensor, out: torch.Tensor | None = None,
+                  size=None) -> torch.Tensor:
+    """packed [P,H+4,W+4,4] + homs [V,P,9] (host or device) -> [V,H,W,3].
+    size = (Ht, Wt): a target frame of its own size [V,Ht,Wt,3] (mpiv_render_packed_tgt): target
+    pixel (x, y) of the Ht x Wt grid through homs, the source pixel coordinate it lands on
+    normalised by the target's (Ht - 1, Wt - 1) as the reference's planar_transform_torch does and
+    sampled over the packed H x W planes.  None: the same-size launch, untouched."""
     _dev(packed)
-    return _render_views("render_packed", packed, packed_hw(packed), homs, out)
+    return _render_views("render_packed", packed, packed_hw(packed), homs, out, size)
 
 
 def render_packed_ct(packed: torch.Tensor, homs: torch.Tensor, back: bool, p_begin: int = 0,

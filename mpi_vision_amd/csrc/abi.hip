@@ -477,21 +477,34 @@ static bool rows_same_oob(int V) {
     return o == 2 || (o == 0 && V <= 2);
 }
 
-static int render_packed_impl(const float* packed, int H, int W, int P, int p_begin, int p_end, int back,
-                              const float* homs, int V, float* out, bool ct, int variant, void* stream) {
-    const char* nm = ct ? "mpiv_render_packed_ct" : "mpiv_render_packed";
+// Hs x Ws: the packed source planes; H x W: the target frame (the same-size entries pass H, W, H, W).
+// A target of its own size (mpiv_render_packed_tgt, `tnm` its name) is a full composite through the
+// production routes -- the kernels' RenderGeomT instantiations (render.hip); with the four
+// dimensions equal in pairs it is the same-size launch itself.
+static int render_packed_impl(const float* packed, int Hs, int Ws, int H, int W, int P, int p_begin, int p_end,
+                              int back, const float* homs, int V, float* out, bool ct, int variant, void* stream,
+                              const char* tnm = nullptr) {
+    const char* nm = tnm ? tnm : ct ? "mpiv_render_packed_ct" : "mpiv_render_packed";
     if (!packed || !homs || !out) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
-    if (V <= 0 || H <= 0 || W <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
+    if (V <= 0 || H <= 0 || W <= 0 || Hs <= 0 || Ws <= 0 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape", nm);
     if (p_begin < 0 || p_end > P || p_begin >= p_end) return fail(MPIV_ERR_ARG, "%s: bad plane range", nm);
     if (!aligned16(packed) || (ct && !aligned16(out))) return fail(MPIV_ERR_ARG, "%s: 16-byte alignment", nm);
-    if ((int64_t)(H + 2 * kPad) * (W + 2 * kPad) * 16 >= (int64_t)kOOB || H >= (1 << 22) || W >= (1 << 22))
+    if ((int64_t)(Hs + 2 * kPad) * (Ws + 2 * kPad) * 16 >= (int64_t)kOOB || Hs >= (1 << 22) || Ws >= (1 << 22) ||
+        H >= (1 << 22) || W >= (1 << 22))
         return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or a side >= 2^22", nm);
+    const bool tgt = Hs != H || Ws != W;
+    if (tgt && (ct || variant != 0))
+        return fail(MPIV_ERR_ARG, "%s: a target of its own size takes the full composite only", nm);
     const float4* pk = reinterpret_cast<const float4*>(packed);
-    const int64_t ps = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
-    const RenderGeom g = make_geom(H, W, P);
-    const bool fast = H >= 2 && W >= 2;  // div_const needs divisors >= 1
+    const int64_t ps = (int64_t)(Hs + 2 * kPad) * (Ws + 2 * kPad);
+    const RenderGeom g = make_geom(Hs, Ws, P);
+    const RenderGeomT gt = make_geom(Hs, Ws, H, W, P);
+    const bool fast = H >= 2 && W >= 2 && Hs >= 2 && Ws >= 2;  // div_const needs divisors >= 1 (H, W: the target's)
     hipStream_t st = S(stream);
 #if MPIV_AB
+    if (tgt && (opt(kOptRenderMv) || opt(kOptRenderRing) > 0 || opt(kOptRenderPair) || opt(kOptRenderTile) > 0 ||
+                opt(kOptRenderVshare) == 1 || opt(kOptRenderVshare) == -1))
+        return fail(MPIV_ERR_ARG, "%s: the A/B kernels render same-size frames only", nm);
     if (variant == 1 && fast && p_end - p_begin <= kLMaxP) {
         // footprints staged through LDS (render_lds.hip)
         const int64_t nb = (int64_t)blocks(W, kLTX) * blocks(H, kLTY) * V;
@@ -588,7 +601,9 @@ static int render_packed_impl(const float* packed, int H, int W, int P, int p_be
     //    render_colsep=-1 turns it off): config 4 at 125 views 25.9 -> 23.5 ms.  With that path (9, 3)
     //    measured 23.3 ms against (6, 3)'s 23.66, without it 26.08 against 25.94: the host cannot tell
     //    which a launch will take, so near-square MPIs keep (6, 3) (profiles/r07_colsep.json).
-    const float sxr = (float)W / (float)(H > 1 ? H - 1 : 1), syr = (float)H / (float)(W > 1 ? W - 1 : 1);
+    // (the sample's advance per output column and row: source extent over the target's swapped
+    // normaliser, Ws/(Ht-1) and Hs/(Wt-1); the tile counts are the target's)
+    const float sxr = (float)Ws / (float)(H > 1 ? H - 1 : 1), syr = (float)Hs / (float)(W > 1 ? W - 1 : 1);
     const bool square = sxr >= 0.8f && sxr <= 1.25f && syr >= 0.8f && syr <= 1.25f;
     const int rows_opt = opt(kOptRenderTile);
     const int64_t rows_blocks = (int64_t)blocks(W, kTileX) * blocks(H, 4 * 8) * V;
@@ -633,8 +648,9 @@ static int render_packed_impl(const float* packed, int H, int W, int P, int p_be
         const bool oob = same && vsd == 4 && rows_same_oob(V);  // R = 6 only
         // the counting build (mpiv_render_packed_census) exists for the automatic choices
         if (g_route)
-            return note_route(nb, 256, "render_rows_kernel<%s, %d, true, false, %d, %s, %s>", ct ? "true" : "false", R,
-                              vsd == 3 || vsd == 11 ? 4 : 3, same ? "true" : "false", oob ? "true" : "false");
+            return note_route(nb, 256, "render_rows_%s<%s, %d, true, false, %d, %s, %s>", tgt ? "tgt_kernel" : "kernel",
+                              ct ? "true" : "false", R, vsd == 3 || vsd == 11 ? 4 : 3, same ? "true" : "false",
+                              oob ? "true" : "false");
         unsigned long long* cn = (g_census && !ct) ? g_census : nullptr;
         if (cn) g_census = nullptr;
         const int csp = opt(kOptRenderColsep);  // the column-separable issue path (render.hip ColSet)
@@ -643,6 +659,9 @@ static int render_packed_impl(const float* packed, int H, int W, int P, int p_be
     if (ct)                                                                                                          \
         render_rows_kernel<true, R, true, false, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(                           \
             pk, ps, g, V, p_begin, p_end, back, homs, out, nullptr, 0, -1, csp, ord);                                \
+    else if (tgt)                                                                                                    \
+        render_rows_tgt_kernel<false, R, true, false, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(                      \
+            pk, ps, gt, V, p_begin, p_end, 1, homs, out, nullptr, 0, -1, csp, ord);                                  \
     else                                                                                                             \
         render_rows_kernel<false, R, true, false, D, SM, OB><<<(unsigned)nb, 256, 0, st>>>(                          \
             pk, ps, g, V, p_begin, p_end, 1, homs, out, nullptr, 0, -1, csp, ord)
@@ -712,9 +731,14 @@ static int render_packed_impl(const float* packed, int H, int W, int P, int p_be
     if (nblocks > kMaxGridX) return fail(MPIV_ERR_ARG, "%s: too many blocks", nm);
     const dim3 grid((unsigned)nblocks), blk(256);
     if (g_route)
-        return note_route(nblocks, 256, "render_packed_kernel<%s, %s>", ct ? "true" : "false", fast ? "true" : "false");
+        return note_route(nblocks, 256, "render_packed_%s<%s, %s>", tgt ? "tgt_kernel" : "kernel", ct ? "true" : "false",
+                          fast ? "true" : "false");
     const int ord = render_tile_order(V);
-    if (ct && fast)
+    if (tgt && fast)
+        render_packed_tgt_kernel<false, true><<<grid, blk, 0, st>>>(pk, ps, gt, V, p_begin, p_end, 1, homs, out, ord);
+    else if (tgt)
+        render_packed_tgt_kernel<false, false><<<grid, blk, 0, st>>>(pk, ps, gt, V, p_begin, p_end, 1, homs, out, ord);
+    else if (ct && fast)
         render_packed_kernel<true, true><<<grid, blk, 0, st>>>(pk, ps, g, V, p_begin, p_end, back, homs, out, ord);
     else if (ct)
         render_packed_kernel<true, false><<<grid, blk, 0, st>>>(pk, ps, g, V, p_begin, p_end, back, homs, out, ord);
@@ -727,14 +751,20 @@ static int render_packed_impl(const float* packed, int H, int W, int P, int p_be
 
 int mpiv_render_packed(const float* packed, int H, int W, int P, const float* homs, int V, float* out,
                        void* stream) {
-    return render_packed_impl(packed, H, W, P, 0, P, 1, homs, V, out, false, 0, stream);
+    return render_packed_impl(packed, H, W, H, W, P, 0, P, 1, homs, V, out, false, 0, stream);
+}
+
+int mpiv_render_packed_tgt(const float* packed, int Hs, int Ws, int P, const float* homs, int V, int Ht, int Wt,
+                           float* out, void* stream) {
+    return render_packed_impl(packed, Hs, Ws, Ht, Wt, P, 0, P, 1, homs, V, out, false, 0, stream,
+                              "mpiv_render_packed_tgt");
 }
 
 int mpiv_render_packed_census(const float* packed, int H, int W, int P, const float* homs, int V, float* out,
                               unsigned long long* census, void* stream) {
     if (!census) return fail(MPIV_ERR_ARG, "mpiv_render_packed_census: null census");
     g_census = census;  // render_packed_impl launches the counting build of the rows kernel
-    const int rc = render_packed_impl(packed, H, W, P, 0, P, 1, homs, V, out, false, 0, stream);
+    const int rc = render_packed_impl(packed, H, W, H, W, P, 0, P, 1, homs, V, out, false, 0, stream);
     const bool used = g_census == nullptr;
     g_census = nullptr;
     if (rc != MPIV_OK) return rc;
@@ -748,12 +778,12 @@ int mpiv_render_packed_lds(const float* packed, int H, int W, int P, const float
     (void)packed, (void)H, (void)W, (void)P, (void)homs, (void)V, (void)out, (void)stream;
     return fail(MPIV_ERR_ARG, "mpiv_render_packed_lds: an A/B kernel, built only into libmpiv_ab.so");
 #endif
-    return render_packed_impl(packed, H, W, P, 0, P, 1, homs, V, out, false, 1, stream);
+    return render_packed_impl(packed, H, W, H, W, P, 0, P, 1, homs, V, out, false, 1, stream);
 }
 
 int mpiv_render_packed_ct(const float* packed, int H, int W, int P, int p_begin, int p_end, int back,
                           const float* homs, int V, float* ct, void* stream) {
-    return render_packed_impl(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, 0, stream);
+    return render_packed_impl(packed, H, W, H, W, P, p_begin, p_end, back, homs, V, ct, true, 0, stream);
 }
 
 // Rows [y_begin, y_end) of mpiv_render_packed_ct's partial: the plane-sharded render issues its
@@ -2577,38 +2607,47 @@ static int unpack_planes_tex(const char* nm, const void* packed, int H, int W, i
 
 // One launch of render_u8_kernel / render_f16_kernel<CT, R, VS, D> (ct picks CT; a full composite
 // replaces the first plane whatever `back` says)
+// gt: the geometry of a target frame of its own size (tgt; the full composite only), g with it
+// the same-size geometry
 template <class T, int R, bool VS, int D>
 static void launch_render_tex(bool ct, int64_t nb, hipStream_t q, const typename T::Texel* pk, int64_t npix,
-                              const RenderGeom& g, const TexGeom& tg, int V, int p_begin, int p_end, int back,
-                              const float* homs, float* out, int csp, int ord) {
+                              const RenderGeom& g, bool tgt, const RenderGeomT& gt, const TexGeom& tg, int V,
+                              int p_begin, int p_end, int back, const float* homs, float* out, int csp, int ord) {
 #define MPIV_TEX(KERNEL)                                                                                            \
-    if (ct) KERNEL<true, R, VS, D><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, tg, V, p_begin, p_end, back, homs, out, \
+    if (ct) KERNEL##_kernel<true, R, VS, D><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, tg, V, p_begin, p_end, back, homs, out, \
                                                                 csp, ord);                                           \
-    else KERNEL<false, R, VS, D><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, tg, V, p_begin, p_end, 1, homs, out, csp, \
+    else if (tgt) KERNEL##_tgt_kernel<R, VS, D><<<(unsigned)nb, 256, 0, q>>>(pk, npix, gt, tg, V, homs, out, csp,    \
+                                                                             ord);                                  \
+    else KERNEL##_kernel<false, R, VS, D><<<(unsigned)nb, 256, 0, q>>>(pk, npix, g, tg, V, p_begin, p_end, 1, homs, out, csp, \
                                                               ord)
     if constexpr (std::is_same<T, TexU8>::value) {
-        MPIV_TEX(render_u8_kernel);
+        MPIV_TEX(render_u8);
     } else {
-        MPIV_TEX(render_f16_kernel);
+        MPIV_TEX(render_f16);
     }
 #undef MPIV_TEX
 }
 
+// Hs x Ws: the packed source planes; H x W: the target frame (render_packed_impl's convention)
 template <class T>
-static int render_tex_impl(const void* packed, int H, int W, int P, int p_begin, int p_end, int back,
-                           const float* homs, int V, float* out, bool ct, void* stream) {
+static int render_tex_impl(const void* packed, int Hs, int Ws, int H, int W, int P, int p_begin, int p_end, int back,
+                           const float* homs, int V, float* out, bool ct, void* stream, const char* tnm = nullptr) {
     constexpr bool u8 = std::is_same<T, TexU8>::value;
-    const char* nm = u8 ? (ct ? "mpiv_render_packed_u8_ct" : "mpiv_render_packed_u8")
-                        : (ct ? "mpiv_render_packed_f16_ct" : "mpiv_render_packed_f16");
+    const char* nm = tnm ? tnm
+                     : u8 ? (ct ? "mpiv_render_packed_u8_ct" : "mpiv_render_packed_u8")
+                          : (ct ? "mpiv_render_packed_f16_ct" : "mpiv_render_packed_f16");
     if (!packed || !homs || !out) return fail(MPIV_ERR_ARG, "%s: null pointer", nm);
-    if (V <= 0 || H < 2 || W < 2 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape (H, W >= 2)", nm);
+    if (V <= 0 || H < 2 || W < 2 || Hs < 2 || Ws < 2 || P <= 0) return fail(MPIV_ERR_ARG, "%s: bad shape (H, W >= 2)", nm);
+    const bool tgt = Hs != H || Ws != W;
+    if (tgt && ct) return fail(MPIV_ERR_ARG, "%s: a target of its own size takes the full composite only", nm);
     if (p_begin < 0 || p_end > P || p_begin >= p_end) return fail(MPIV_ERR_ARG, "%s: bad plane range", nm);
     if (tex_misaligned<T>(packed) || (ct && !aligned16(out)))
         return fail(MPIV_ERR_ARG, "%s: alignment (packed %d B, ct 16 B)", nm, (int)T::kBytes);
-    const int64_t npix = (int64_t)(H + 2 * kPad) * (W + 2 * kPad);
-    if (npix * T::kBytes >= (int64_t)kOOB || H >= (1 << 22) || W >= (1 << 22))
+    const int64_t npix = (int64_t)(Hs + 2 * kPad) * (Ws + 2 * kPad);
+    if (npix * T::kBytes >= (int64_t)kOOB || Hs >= (1 << 22) || Ws >= (1 << 22) || H >= (1 << 22) || W >= (1 << 22))
         return fail(MPIV_ERR_ARG, "%s: padded plane larger than 2 GiB or a side >= 2^22", nm);
-    const RenderGeom g = make_geom(H, W, P);
+    const RenderGeom g = make_geom(Hs, Ws, P);
+    const RenderGeomT gt = make_geom(Hs, Ws, H, W, P);
     TexGeom tg;
     tg.row = g.Wp * T::kBytes;
     tg.org = (kPad * g.Wp + kPad) * T::kBytes;
@@ -2619,7 +2658,8 @@ static int render_tex_impl(const void* packed, int H, int W, int P, int p_begin,
     // Stretched MPIs (swapped x/(H-1) normalisation) take it only when the launch fills the chip
     // (>= 2048 tiles of 64x32, as the float route): config 2 at one view 0.080-0.089 vs 0.065 ms
     // for 2 plain rows, at 64 views 2.35 vs 2.40-2.49.
-    const float sxr = (float)W / (float)(H - 1), syr = (float)H / (float)(W - 1);
+    // (the sample's advance: source extent over the target's normaliser; tile counts: the target's)
+    const float sxr = (float)Ws / (float)(H - 1), syr = (float)Hs / (float)(W - 1);
     const bool square = sxr >= 0.8f && sxr <= 1.25f && syr >= 0.8f && syr <= 1.25f;
     const bool big = (int64_t)blocks(W, kTileX) * blocks(H, 4 * 8) * V >= 2048;
     // The debug options pick u8 variants only (the f16 render ignores them).
@@ -2637,13 +2677,14 @@ static int render_tex_impl(const void* packed, int H, int W, int P, int p_begin,
     const int f = fo ? fo : (nb < 2048 ? 4 : 2);
     const int d = (vs && R == 4 && (f == 4 || f == 8)) ? f : 2;
     if (g_route)  // every template argument, as rocprof's demangled name shows it
-        return note_route(nb, 256, "render_%s_kernel<%s, %d, %s, %d>", u8 ? "u8" : "f16", ct ? "true" : "false", R,
-                          vs ? "true" : "false", d);
+        return tgt ? note_route(nb, 256, "render_%s_tgt_kernel<%d, %s, %d>", u8 ? "u8" : "f16", R, vs ? "true" : "false", d)
+                   : note_route(nb, 256, "render_%s_kernel<%s, %d, %s, %d>", u8 ? "u8" : "f16", ct ? "true" : "false", R,
+                                vs ? "true" : "false", d);
     const int csp = opt(kOptRenderColsep);  // the column-separable issue path (render.hip ColSet)
     const int ord = render_tile_order(V);
 #define MPIV_TEX(RR, VV, DD)                                                                                        \
-    launch_render_tex<T, RR, VV, DD>(ct, nb, S(stream), static_cast<const typename T::Texel*>(packed), npix, g, tg, \
-                                     V, p_begin, p_end, back, homs, out, csp, ord)
+    launch_render_tex<T, RR, VV, DD>(ct, nb, S(stream), static_cast<const typename T::Texel*>(packed), npix, g, tgt, \
+                                     gt, tg, V, p_begin, p_end, back, homs, out, csp, ord)
     if constexpr (u8) {  // the variants only the 8-bit format has
 #if MPIV_AB
         if (R == 8) {  // 8 rows per work-item (A/B)
@@ -2688,22 +2729,34 @@ int mpiv_unpack_planes_f16(const uint16_t* packed, int H, int W, int P, float* o
 
 int mpiv_render_packed_u8(const uint32_t* packed, int H, int W, int P, const float* homs, int V, float* out,
                           void* stream) {
-    return render_tex_impl<TexU8>(packed, H, W, P, 0, P, 1, homs, V, out, false, stream);
+    return render_tex_impl<TexU8>(packed, H, W, H, W, P, 0, P, 1, homs, V, out, false, stream);
 }
 
 int mpiv_render_packed_u8_ct(const uint32_t* packed, int H, int W, int P, int p_begin, int p_end, int back,
                              const float* homs, int V, float* ct, void* stream) {
-    return render_tex_impl<TexU8>(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
+    return render_tex_impl<TexU8>(packed, H, W, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
 }
 
 int mpiv_render_packed_f16(const uint16_t* packed, int H, int W, int P, const float* homs, int V, float* out,
                            void* stream) {
-    return render_tex_impl<TexF16>(packed, H, W, P, 0, P, 1, homs, V, out, false, stream);
+    return render_tex_impl<TexF16>(packed, H, W, H, W, P, 0, P, 1, homs, V, out, false, stream);
+}
+
+int mpiv_render_packed_u8_tgt(const uint32_t* packed, int Hs, int Ws, int P, const float* homs, int V, int Ht, int Wt,
+                              float* out, void* stream) {
+    return render_tex_impl<TexU8>(packed, Hs, Ws, Ht, Wt, P, 0, P, 1, homs, V, out, false, stream,
+                                  "mpiv_render_packed_u8_tgt");
+}
+
+int mpiv_render_packed_f16_tgt(const uint16_t* packed, int Hs, int Ws, int P, const float* homs, int V, int Ht, int Wt,
+                               float* out, void* stream) {
+    return render_tex_impl<TexF16>(packed, Hs, Ws, Ht, Wt, P, 0, P, 1, homs, V, out, false, stream,
+                                   "mpiv_render_packed_f16_tgt");
 }
 
 int mpiv_render_packed_f16_ct(const uint16_t* packed, int H, int W, int P, int p_begin, int p_end, int back,
                               const float* homs, int V, float* ct, void* stream) {
-    return render_tex_impl<TexF16>(packed, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
+    return render_tex_impl<TexF16>(packed, H, W, H, W, P, p_begin, p_end, back, homs, V, ct, true, stream);
 }
 
 // ---- alpha-only planes under per-plane colours (render_texel.hip TexA32) ----
@@ -2799,9 +2852,11 @@ int mpiv_route(const char* entry, const int64_t* a, int na, char* name, int name
     int rc;
     g_route = &note;
     if (strcmp(entry, "render_packed") == 0 && na == 4)
-        rc = render_packed_impl(d, (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d, false, 0, nullptr);
+        rc = render_packed_impl(d, (int)a[0], (int)a[1], (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d, false, 0,
+                                nullptr);
     else if (strcmp(entry, "render_packed_ct") == 0 && na == 4)
-        rc = render_packed_impl(d, (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d, true, 0, nullptr);
+        rc = render_packed_impl(d, (int)a[0], (int)a[1], (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d, true, 0,
+                                nullptr);
     else if (strcmp(entry, "render_packed_ct_rows") == 0 && na == 6)
         rc = mpiv_render_packed_ct_rows(d, (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], (int)a[4],
                                         (int)a[5], d, nullptr);
@@ -2818,10 +2873,20 @@ int mpiv_route(const char* entry, const int64_t* a, int na, char* name, int name
         rc = mpiv_render_backward(d, st, (int)a[0], (int)a[1], (int)a[2], (int)P, d, d, ck, d, d,
                                   mpiv_render_backward_workspace_size((int)a[1], (int)a[2], (int)P), nullptr);
     } else if (strcmp(entry, "render_packed_u8") == 0 && na == 4) {
-        rc = render_tex_impl<TexU8>(d, (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d, false, nullptr);
+        rc = render_tex_impl<TexU8>(d, (int)a[0], (int)a[1], (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d,
+                                    false, nullptr);
     } else if ((strcmp(entry, "render_packed_f16") == 0 || strcmp(entry, "render_packed_f16_ct") == 0) && na == 4) {
-        rc = render_tex_impl<TexF16>(d, (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d,
+        rc = render_tex_impl<TexF16>(d, (int)a[0], (int)a[1], (int)a[0], (int)a[1], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d,
                                      strcmp(entry, "render_packed_f16_ct") == 0, nullptr);
+    } else if (strcmp(entry, "render_packed_tgt") == 0 && na == 6) {  // Hs, Ws, P, V, Ht, Wt
+        rc = render_packed_impl(d, (int)a[0], (int)a[1], (int)a[4], (int)a[5], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d,
+                                false, 0, nullptr, "mpiv_render_packed_tgt");
+    } else if (strcmp(entry, "render_packed_u8_tgt") == 0 && na == 6) {
+        rc = render_tex_impl<TexU8>(d, (int)a[0], (int)a[1], (int)a[4], (int)a[5], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d,
+                                    false, nullptr, "mpiv_render_packed_u8_tgt");
+    } else if (strcmp(entry, "render_packed_f16_tgt") == 0 && na == 6) {
+        rc = render_tex_impl<TexF16>(d, (int)a[0], (int)a[1], (int)a[4], (int)a[5], (int)a[2], 0, (int)a[2], 1, d, (int)a[3], d,
+                                     false, nullptr, "mpiv_render_packed_f16_tgt");
     } else if (strcmp(entry, "render_packed_alpha") == 0 && na == 4) {
         rc = mpiv_render_packed_alpha(d, (int)a[0], (int)a[1], (int)a[2], d, d, (int)a[3], d, nullptr);
     } else if (strcmp(entry, "render_net_output") == 0 && na == 4) {

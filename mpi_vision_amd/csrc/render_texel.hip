@@ -474,13 +474,15 @@ __device__ __forceinline__ void render_tex_vs_pixels(const typename T::Texel* __
 // 256-thread block = 64 x 4R tile, XCD-aware (tile, view) order, tile-level division proof; a tile
 // where the proof fails runs the per-sample guarded recipe (GUARD); a tile every plane of which
 // samples the zero border composites zeros (render.hip tile_dead).
-template <class T, bool CT, int R, bool VS, int D>
+// G: RenderGeom, or RenderGeomT for a target frame of its own size (render.hip): the tiling, the
+// bounds and the output index follow the target grid, everything on the sample path the source.
+template <class T, bool CT, int R, bool VS, int D, class G>
 __device__ __forceinline__ void render_tex_tile(const typename T::Texel* __restrict__ planes, int64_t plane_stride,
-                                                const RenderGeom& g, const TexGeom& tg, int V, int p_begin, int p_end,
+                                                const G& g, const TexGeom& tg, int V, int p_begin, int p_end,
                                                 int back, const float* __restrict__ homs, float* __restrict__ out,
                                                 int colsep, int order, const float* __restrict__ colors = nullptr) {
     constexpr int TY = 4 * R;
-    const int tiles_x = (g.W + kTileX - 1) / kTileX;
+    const int tiles_x = (tgt_w(g) + kTileX - 1) / kTileX;
     const int lb = xcd_logical_block(blockIdx.x, gridDim.x);
     const int v = lb % V;
     const int tile = xcd_tile_order(lb / V, (int)gridDim.x / V, tiles_x, order);  // render.hip
@@ -490,8 +492,8 @@ __device__ __forceinline__ void render_tex_tile(const typename T::Texel* __restr
     const float* hv = homs + (int64_t)v * g.P * 9;
     bool ok = true, dd = true, cs = true;
     {
-        const float x0 = (float)tx0, x1 = (float)min(tx0 + kTileX - 1, g.W - 1);
-        const float fy0 = (float)ty0, fy1 = (float)min(ty0 + TY - 1, g.H - 1);
+        const float x0 = (float)tx0, x1 = (float)min(tx0 + kTileX - 1, tgt_w(g) - 1);
+        const float fy0 = (float)ty0, fy1 = (float)min(ty0 + TY - 1, tgt_h(g) - 1);
         for (int p = p_begin + (int)threadIdx.x; p < p_end; p += 256) {
             const float* hp = hv + (int64_t)p * 9;
             const bool safe = div2_rect_safe(hp, x0, x1, fy0, fy1);
@@ -506,7 +508,7 @@ __device__ __forceinline__ void render_tex_tile(const typename T::Texel* __restr
     bool sep = false;
     if constexpr (VS)
         sep = tg.row < kColsepMaxPitch && (colsep > 0 || (colsep == 0 && __syncthreads_and(cs)));
-    if (x >= g.W || y0 >= g.H) return;  // rows past H inside [y0, y0+R) are computed, not stored
+    if (x >= tgt_w(g) || y0 >= tgt_h(g)) return;  // rows past H inside [y0, y0+R) are computed, not stored
     float cr[R], cg[R], cb[R], tt[R];
 #pragma unroll
     for (int k = 0; k < R; ++k) {
@@ -538,8 +540,8 @@ __device__ __forceinline__ void render_tex_tile(const typename T::Texel* __restr
 #pragma unroll
     for (int k = 0; k < R; ++k) {
         const int y = y0 + k;
-        if (y >= g.H) break;
-        const int64_t o = ((int64_t)v * g.H + y) * g.W + x;
+        if (y >= tgt_h(g)) break;
+        const int64_t o = ((int64_t)v * tgt_h(g) + y) * tgt_w(g) + x;
         if (CT) {
             reinterpret_cast<float4*>(out)[o] = make_float4(cr[k], cg[k], cb[k], tt[k]);
         } else {
@@ -567,6 +569,24 @@ __global__ __launch_bounds__(256) void render_f16_kernel(const uint2* __restrict
                                                          float* __restrict__ out, int colsep = 0, int order = 0) {
     render_tex_tile<TexF16, CT, R, VS, D>(planes, plane_stride, g, tg, V, p_begin, p_end, back, homs, out, colsep,
                                           order);
+}
+
+// The full composite into a target frame of its own size [V,Ht,Wt,3] (mpiv_render_packed_u8_tgt,
+// mpiv_render_packed_f16_tgt; render.hip RenderGeomT).
+template <int R, bool VS, int D>
+__global__ __launch_bounds__(256) void render_u8_tgt_kernel(const unsigned* __restrict__ planes, int64_t plane_stride,
+                                                            RenderGeomT g, TexGeom tg, int V,
+                                                            const float* __restrict__ homs, float* __restrict__ out,
+                                                            int colsep, int order) {
+    render_tex_tile<TexU8, false, R, VS, D>(planes, plane_stride, g, tg, V, 0, g.P, 1, homs, out, colsep, order);
+}
+
+template <int R, bool VS, int D>
+__global__ __launch_bounds__(256) void render_f16_tgt_kernel(const uint2* __restrict__ planes, int64_t plane_stride,
+                                                             RenderGeomT g, TexGeom tg, int V,
+                                                             const float* __restrict__ homs, float* __restrict__ out,
+                                                             int colsep, int order) {
+    render_tex_tile<TexF16, false, R, VS, D>(planes, plane_stride, g, tg, V, 0, g.P, 1, homs, out, colsep, order);
 }
 
 // Alpha-only planes under per-plane colours [P,3] (TexA32): the full composite only (no (C, T)

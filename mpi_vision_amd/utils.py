@@ -256,6 +256,112 @@ def mpi_render_view_f16(rgba_layers_f16, tgt_pose, planes, intrinsics):
     return _lib.render_f16_views(rgba_layers_f16, homs)  # (pack + packed render, view by view or once)
 
 
+def _render_view2_chain(rgba_layers, tgt_pose, depths, src_intrinsics, tgt_intrinsics, tgt_height, tgt_width):
+    """mpi_render_view_torch2's definition, helper by helper: the reference's mpi_render_view_torch
+    (utils.py:267-294 -> 237-265) with k_t and the target grid opened up.  P warped [B,4,Ht,Wt] planes
+    and P + 2 launches; differentiable w.r.t. rgba_layers (the sampler's and the compositor's HIP
+    adjoints)."""
+    n_planes, batch = depths.shape[0], tgt_pose.shape[0]
+    d = depths.repeat(1, batch)
+    imgs = rgba_layers.permute(3, 0, 1, 2, 4)
+    rot, t = tgt_pose[:, :3, :3], tgt_pose[:, :3, 3:]
+    n_hat = torch.tensor([0.0, 0.0, 1.0], device=tgt_pose.device).reshape(1, 1, 1, 3).repeat(n_planes, batch, 1, 1)
+    a = -d.reshape(n_planes, batch, 1, 1)
+    grid = meshgrid_abs_torch(batch, tgt_height, tgt_width).permute(0, 2, 3, 1).to(rgba_layers.device)
+    warped = planar_transform_torch(imgs, grid, src_intrinsics, tgt_intrinsics, rot, t, n_hat, a)
+    warped = warped.permute(0, 1, 3, 4, 2)
+    return over_composite([warped[i] for i in range(n_planes)])
+
+
+def mpi_render_view_torch2(rgba_layers, tgt_pose, planes, src_intrinsics, tgt_intrinsics, tgt_height, tgt_width):
+    """Render an MPI [B, Hs, Ws, P, 4] into a target camera of its own size and intrinsics:
+    [B, tgt_height, tgt_width, 3] fp32.  Bit for bit over_composite of the P planes of
+
+        planar_transform_torch(rgba_layers.permute(3, 0, 1, 2, 4),
+                               meshgrid_abs_torch(B, tgt_height, tgt_width).permute(0, 2, 3, 1),
+                               src_intrinsics, tgt_intrinsics, rot, t, n_hat, -depths)
+
+    -- what the reference computes inside mpi_render_view_torch (utils.py:267-294) with the two places
+    where it reuses `intrinsics` and `height, width` opened up (planar_transform_torch already takes
+    k_s, k_t and a target grid of any size, utils.py:198-233) -- as ONE fused HIP kernel: no warped
+    plane and no sampling grid is written.  mpi_render_view_torch2(x, pose, planes, K, K, H, W) equals
+    mpi_render_view_torch(x, pose, planes, K).
+
+    The reference normalises the source pixel coordinate a target pixel lands on by the TARGET grid,
+    swapped (x / (Ht - 1), y / (Wt - 1), utils.py:186-188), and grid_sample unnormalises over the
+    source: a source pixel coordinate x_s is sampled at x_s * Ws / (Ht - 1) - 0.5 and y_s at
+    y_s * Hs / (Wt - 1) - 0.5.  So the homography's source coordinates span 0 .. Ht - 1 and
+    0 .. Wt - 1 whatever the MPI's size: express BOTH intrinsics at the target's resolution
+    (supersampling an MPI 2x: scale its intrinsics by 2 for both arguments).  For a crop window
+    [y0 : y0 + h, x0 : x0 + w] of a full frame, the target is h x w: src_intrinsics is the MPI's camera
+    scaled to the WINDOW's size (h, w), and tgt_intrinsics is the full frame's camera with only its
+    principal point shifted by the window's origin (cx - x0, cy - y0).
+
+    rgba_layers: float32 as defined; uint8 as in mpi_render_view_u8 (exactly the float definition
+    on x.float() / 255, from 4-B texels); float16 as in mpi_render_view_f16 (exactly the definition on
+    x.float(), from 8-B texels); any other dtype raises.  `planes` must be a tensor (a list raises
+    AttributeError as in the reference).  A stride-0 batch is packed once and rendered in one launch,
+    any other batch view by view into one output.  Cameras on the host or the device (the autograd
+    route too); under a HIP-graph capture host poses raise, and so do source intrinsics on the host
+    (their upload cannot be part of the graph).
+
+    The fused render follows the fused-multiply-add chain of the reference's batched matmul, which
+    ATen uses from 45 target pixels (Ht * Wt >= 45); smaller targets, where ATen sums plain products
+    (_lib.aten_plain), can differ from the helper chain in the last bit of a sample position.
+
+    Autograd: with grad enabled and a float32 rgba_layers that requires grad, the helper chain itself
+    runs (planar_transform_torch + over_composite, P warped planes) and d rgba_layers comes back from
+    their HIP adjoints.  A float16 MPI requiring grad raises (pass .float()); a uint8 MPI has no
+    gradient.  Camera gradients exist for the same-size render only: tgt_pose, planes or an
+    intrinsics tensor requiring grad raises RuntimeError.  An extension of the drop-in API."""
+    batch_size = tgt_pose.shape[0]
+    n_planes = len(planes)
+    depths = planes.reshape([n_planes, 1])  # AttributeError on a list, like the reference
+    if not isinstance(rgba_layers, torch.Tensor) or rgba_layers.dtype not in (torch.float32, torch.uint8, torch.float16):
+        raise RuntimeError("mpi_render_view_torch2 expects a float32, uint8 or float16 MPI, got "
+                           f"{getattr(rgba_layers, 'dtype', type(rgba_layers).__name__)}")
+    if rgba_layers.dim() != 5 or rgba_layers.shape[-1] != 4:
+        raise RuntimeError(f"rgba_layers must be [B,H,W,P,4], got {tuple(rgba_layers.shape)}")
+    B, _, _, P, _ = rgba_layers.shape
+    if B != batch_size or P != n_planes:
+        raise RuntimeError(f"shape mismatch: MPI batch/planes {B}/{P} vs poses/planes {batch_size}/{n_planes}")
+    size = _lib._target_size((tgt_height, tgt_width))
+    if rgba_layers.device.type != "cuda":
+        raise RuntimeError("mpi_vision_amd kernels need ROCm device tensors "
+                           f"(got a tensor on {rgba_layers.device}); there is no CPU path")
+    if torch.is_grad_enabled():
+        if any(isinstance(x, torch.Tensor) and x.requires_grad
+               for x in (tgt_pose, planes, src_intrinsics, tgt_intrinsics)):
+            raise RuntimeError("mpi_render_view_torch2: camera gradients (tgt_pose, planes, intrinsics) exist for the "
+                               "same-size render only (mpi_render_view_torch); detach the camera arguments")
+        if rgba_layers.requires_grad:
+            if rgba_layers.dtype != torch.float32:
+                raise RuntimeError("mpi_render_view_torch2: a float16 MPI is not differentiable here; pass "
+                                   "rgba_layers.float()")
+            return _render_view2_chain(rgba_layers, tgt_pose, depths, src_intrinsics, tgt_intrinsics, *size)
+    if tgt_pose.is_cuda:  # poses in HBM: the chain runs there too
+        homs = _host.render_homographies_device(tgt_pose, depths.reshape(-1), src_intrinsics, batch_size,
+                                                tgt_intrinsics=tgt_intrinsics)
+    else:
+        _lib.host_under_capture("tgt_pose")  # host poses cannot be part of a captured HIP graph
+        homs = _host.render_homographies(tgt_pose, depths.reshape(-1), src_intrinsics, batch_size, pin=True,
+                                         tgt_intrinsics=tgt_intrinsics)
+    homs = homs.reshape(B, P, 9)
+    pack, render = {torch.float32: (_lib.pack_planes, _lib.render_packed),
+                    torch.uint8: (_lib.pack_planes_u8, lambda *a, **k: _lib.render_packed_u8(*a, route_float=False, **k)),
+                    torch.float16: (_lib.pack_planes_f16,
+                                    lambda *a, **k: _lib.render_packed_f16(*a, route_float=False, **k))}[rgba_layers.dtype]
+    mpi = rgba_layers.detach()
+    if B > 1 and mpi.stride(0) == 0:  # one MPI, many views: pack once, one launch
+        return render(pack(mpi[0]), homs, size=size)
+    out = torch.empty((B,) + size + (3,), device=mpi.device, dtype=torch.float32)
+    packed = None
+    for b in range(B):
+        packed = pack(mpi[b], out=packed)
+        render(packed, homs[b:b + 1], out=out[b:b + 1], size=size)
+    return out
+
+
 def _plane_color_mpi(rgba_layers, plane_colors):
     """The float MPI the plane-colour render is defined on: RGB = plane_colors[p] all over plane p,
     alpha = rgba_layers' last channel (torch ops: differentiable w.r.t. both)."""
